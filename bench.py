@@ -19,8 +19,17 @@ device (``pomcp_merge_roots``), so ``ms_per_step`` is that planner's
 ``get_action`` latency for S simulations.  ``--deep`` is SURVEY §8(d)'s
 rollout-dominated point (gamma 0.99, epsilon 0.01: depth_limit 459).
 
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON
+line.  ``--full`` adds what takes runs of its own: the CPU baseline (the oracle
+on the host cores) and, for the default workload, the secondary-configuration
+records (``sub``).  ``--dump-outputs DIR`` writes what the last timed step
+computed (every tree's root statistics and every planner's merged decision) as
+``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared array
+for array.
+
     python bench.py [--gpus N --steps K --warmup W --trees B --sims S
-                     --root-parallel K --deep --env E --planner P]
+                     --root-parallel K --deep --env E --planner P
+                     --full --dump-outputs DIR]
 """
 import argparse
 import json
@@ -28,6 +37,8 @@ import math
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "posggym-baselines_amd")):
@@ -215,7 +226,15 @@ def parse():
                          "planner, merged on the device each step (1 = independent planners)")
     ap.add_argument("--deep", action="store_true",
                     help="gamma=0.99, epsilon=0.01 (depth_limit 459, rollout-dominated)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline "
+                         "and, for the default workload, the secondary-configuration "
+                         "records (`sub`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (root statistics per tree, "
+                         "the merged decision per planner) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--update-step", action="store_true",
                     help="each timed step = search + the environment's answer + update() "
                          "(re-root, extraction, reinvigoration, subtree compaction) instead of a "
@@ -224,8 +243,8 @@ def parse():
                     help="cut-off children deferred to the re-root (pomcp_set_defer_cutoff): "
                          "auto = the planners' default (on)")
     ap.add_argument("--no-sub", action="store_true",
-                    help="skip the secondary-configuration records (`sub`) the default run "
-                         "appends after the headline (profiling runs)")
+                    help="with --full: skip the secondary-configuration records (`sub`) "
+                         "appended after the headline")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of N > 1 ranks: nccl (= RCCL over xGMI, the "
                          "measurement) or gloo (tests: several ranks sharing one GPU)")
@@ -237,6 +256,8 @@ def parse():
                     help="host processes for the CPU baseline (capped by os.cpu_count(); the "
                          "GPU box's CPU share is 16)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.sims is None:
         args.sims = 256 if args.planner == "intmcp" else 65536
     if args.trees % args.root_parallel:
@@ -377,7 +398,7 @@ def cpu_baseline_intmcp(sims, pairs, seed, env="Driving-v1"):
                       "oracle/intmcp.py, 1 thread"}
 
 
-def run_intmcp(dev, B, S, env, steps, warmup, seed=0, arena=None):
+def run_intmcp(dev, B, S, env, steps, warmup, seed=0, arena=None, dump=False):
     """I-NTMCP nesting level 1 (BASELINE config 5): B planner pairs x S
     simulations per level, one batched k_im_search launch per step.  Returns
     the bench fields (value, ms_per_step, roofline, config)."""
@@ -454,6 +475,7 @@ def run_intmcp(dev, B, S, env, steps, warmup, seed=0, arena=None):
             nodes += s.n_nodes[0] + s.n_nodes[1] - s0[2]
             stats += s.n_stats[0] + s.n_stats[1] - s0[3]
         nodes_used = max(max(s.n_nodes[0], s.n_nodes[1]) for s in st)
+        outputs = _root_outputs(st, A) if dump else None
     finally:
         bp.close()
     sims_timed = 2 * S * searched * steps
@@ -467,7 +489,7 @@ def run_intmcp(dev, B, S, env, steps, warmup, seed=0, arena=None):
     achieved_hbm = alg_bytes_hbm / (kernel_ms * 1e-3) / 1e9
     traffic = _pmc_traffic("pmc_intmcp.json", lib_sha, trees=B, sims=S, env=env)
     return {
-        "value": sims_timed / elapsed, "ms_per_step": elapsed * 1e3 / steps,
+        "value": sims_timed / elapsed, "ms_per_step": elapsed * 1e3 / steps, "outputs": outputs,
         "workload": f"I-NTMCP nesting 1 {env}, {B} planner pairs x {S} sims per level x 2 levels "
                     "per step (one batched launch), ucb c=sqrt2 gamma=0.95 depth_limit=2",
         "config": {"pairs": B, "sims_per_level": S, "pairs_searched": searched,
@@ -493,7 +515,9 @@ def main_intmcp(args):
     torch.cuda.set_device(0)
     dev = torch.cuda.current_device()
     r = run_intmcp(dev, args.trees, args.sims, args.env, args.steps, args.warmup, args.seed,
-                   args.arena)
+                   args.arena, dump=bool(args.dump_outputs))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, r["outputs"])
     out = {
         "metric": f"I-NTMCP simulations/sec on {args.env} (nesting level 1, exact search)",
         "value": r["value"],
@@ -510,13 +534,14 @@ def main_intmcp(args):
         "config": dict({"workload": r["workload"]}, **r["config"]),
         "roofline": r["roofline"],
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_intmcp(2048, 16, args.seed, args.env)
     print(json.dumps(out), flush=True)
 
 
 def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blocks=512,
-              world=1, rank=0, dist=None, update_step=False, clocks=False, defer=None):
+              world=1, rank=0, dist=None, update_step=False, clocks=False, defer=None,
+              dump=False):
     """`steps` timed POMCP steps on B synthetic roots (S simulations each; K
     replica trees per planner, merged on the device).  A step is restore() +
     one k_search launch + the root-parallel exchange, or with `update_step` a
@@ -566,6 +591,7 @@ def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blo
         merge = merge_buffer_tensor(bp.engine, f"cuda:{dev}")
         gather = gather_buffer_tensor(bp.engine, world, f"cuda:{dev}") if world > 1 else None
         upd_ms = []
+        last = {}
 
         def step(events=None):
             with torch.cuda.stream(stream):
@@ -579,6 +605,7 @@ def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blo
                 if events is not None:
                     events[1].record(stream)
                 if update_step:
+                    last["actions"] = acts
                     obs = bp.engine.synthetic_step(1000, acts)
                     t1 = time.perf_counter()
                     bp.engine.update(acts, obs)   # synchronises
@@ -621,7 +648,8 @@ def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blo
             with torch.cuda.stream(stream):
                 bp.search(fetch=False)
             torch.cuda.synchronize()
-        st = list(bp.engine.root_stats())
+        raw_stats = bp.engine.root_stats()
+        st = list(raw_stats)
         sims = sum(s.num_sims for s in st)          # counted by the kernel, last timed launch
         levels = sum(s.n_levels for s in st)
         deferred = sum(s.n_deferred for s in st)
@@ -633,6 +661,17 @@ def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blo
             merged = bp.engine.merge_roots(K, world=world if world > 1 else 0)   # checks errors
             if not all(0 <= m.action < A for m in merged):
                 raise SystemExit("merged action out of range")
+        outputs = None
+        if dump:
+            outputs = _root_outputs(raw_stats, A)
+            if update_step:   # the actions the last timed step handed to its update()
+                outputs["step_actions"] = np.asarray(last["actions"], dtype=np.float64)
+            else:
+                m = np.ctypeslib.as_array(merged)
+                for k in ("action", "num_sims", "root_visits"):
+                    outputs["merged_" + k] = m[k].astype(np.float64)
+                for k in ("visits", "totals"):
+                    outputs["merged_" + k] = m[k][:, :A].astype(np.float64)
     finally:
         bp.close()
     # tm: + the action_probs of every stepped node (+ 8A written per leaf expansion)
@@ -657,6 +696,7 @@ def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blo
     r = {
         "value": value, "ms_per_step": elapsed * 1e3 / steps, "counted": counted,
         "sims_per_step": sims, "B": B, "caps": caps, "clocks": clk.samples, "lib_sha": lib_sha,
+        "outputs": outputs,
         "workload": f"{'POTMMCP' if tm else 'POMCP'} {env_desc} exact search, {B} roots{note} "
                     f"x {S} sims per GPU, {cfg.action_selection} c=sqrt2 "
                     f"gamma={cfg.discount} depth_limit={cfg.depth_limit}, "
@@ -686,6 +726,33 @@ def run_pomcp(dev, *, env, B, S, K, base_cfg, tm, steps, warmup, seed=0, max_blo
     if update_step:
         r["update_ms"] = sum(upd_ms) / max(1, len(upd_ms))
     return r
+
+
+def _root_outputs(st, A):
+    """Every tree's root record after the last timed search (the root_stats()
+    array a caller of the search receives) as float64 arrays."""
+    a = np.ctypeslib.as_array(st)
+    out = {k: a[k].astype(np.float64) for k in ("action", "num_sims", "root_visits",
+                                                "search_depth", "root_absorbing")}
+    for k in ("child_visits", "child_values", "child_totals"):
+        out[k] = a[k][:, :A].astype(np.float64)
+    return out
+
+
+DUMP_BYTES_MAX = 64 * 10**6
+
+
+def write_outputs(path, outputs):
+    """DIR/<name>.npy per array; an array over its share of DUMP_BYTES_MAX is
+    cut to a fixed (seeded, sorted) sample of its rows."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(outputs))
+    for name, arr in outputs.items():
+        row = max(1, arr.nbytes // max(1, len(arr)))
+        if arr.nbytes > share:
+            keep = np.random.default_rng(0).choice(len(arr), share // row, replace=False)
+            arr = arr[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr))
 
 
 class _NoClocks:
@@ -853,7 +920,7 @@ def main():
         base_cfg = TM_CFG
     # (no CPU leg for POTMMCP: the oracle has no restatement of it -- its parity
     # is pinned to the reference's own records)
-    if rank == 0 and not args.no_cpu_baseline and not tm:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not tm:
         # before any GPU call: the worker processes are forked from this one.
         # With N ranks rank 0 runs it before the process group forms (the other
         # ranks wait in its rendezvous), so every line carries its CPU baseline;
@@ -896,7 +963,10 @@ def main():
                   warmup=args.warmup, seed=args.seed, max_blocks=args.max_blocks, world=world,
                   rank=rank, dist=dist if world > 1 else None, clocks=True,
                   update_step=args.update_step,
-                  defer=None if args.defer == "auto" else args.defer == "on")
+                  defer=None if args.defer == "auto" else args.defer == "on",
+                  dump=bool(args.dump_outputs) and rank == 0)
+    if rank == 0 and args.dump_outputs:   # rank 0's trees (every rank merges the same records)
+        write_outputs(args.dump_outputs, r["outputs"])
     caps = r["caps"]
     out = {
         "metric": (f"MCTS simulations/sec on {args.env} (POTMMCP exact search, fixed-distribution "
@@ -938,7 +1008,7 @@ def main():
         out["cpu_baseline"] = cpu
     default_run = (world == 1 and not tm and not args.deep and args.env == "Driving-v1"
                    and B == 65536 and S == 65536 and K == 1 and not args.update_step)
-    if rank == 0 and default_run and not args.no_sub:
+    if rank == 0 and args.full and default_run and not args.no_sub:
         out["sub"] = sub_records(dev, args.seed)
     if rank == 0:
         print(json.dumps(out), flush=True)

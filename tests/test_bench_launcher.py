@@ -65,6 +65,40 @@ def test_gpus_2_on_a_one_gpu_box_exits_nonzero():
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline line only (the CPU baseline and the `sub`
+    records need --full) and --dump-outputs writes the last timed step's root
+    records and merged decisions as float64 arrays: 260 trees (more than one
+    workgroup, no multiple of the wave) in 65 planners of 4 replicas."""
+    import numpy as np
+    B, S, K = 260, 64, 4
+    r = _run(["--gpus", "1", "--trees", str(B), "--sims", str(S), "--root-parallel", str(K),
+              "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert "cpu_baseline" not in d and "sub" not in d
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "simulations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in sorted(os.listdir(tmp_path / "out"))}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["child_visits"].shape == got["child_values"].shape == (B, 5)
+    assert got["merged_visits"].shape == got["merged_totals"].shape == (B // K, 5)
+    assert got["action"].shape == (B,) and got["merged_action"].shape == (B // K,)
+    searched = got["root_absorbing"] == 0
+    assert searched.any()
+    assert (got["num_sims"][searched] == S).all()
+    assert (got["child_visits"].sum(axis=1)[searched] == S).all()
+    # a planner's merged record is the sum of its replicas' records, in replica order
+    whole = searched.reshape(B // K, K).all(axis=1)
+    assert whole.any()
+    assert (got["merged_visits"][whole]
+            == got["child_visits"].reshape(B // K, K, 5).sum(axis=1)[whole]).all()
+    assert sum(a.nbytes for a in got.values()) < 64 * 2**20
+
+
+@pytest.mark.gpu
 def test_two_ranks_sharing_one_gpu_print_one_line():
     """The launcher, rendezvous, exchange (all-gather + device merge), barrier
     and max-over-ranks timing of N = 2 ranks, both on GPU 0 over gloo (one

@@ -5,8 +5,8 @@
 set -e
 TAG=${1:-r1}
 shift || true
-# --no-sub: only the named configuration's launches (the default bench run appends
-# secondary-configuration records whose kernels would mix into the trace)
+# --no-sub: only the named configuration's launches, also when --full is among the
+# bench args (its secondary-configuration records' kernels would mix into the trace)
 ARGS="--no-sub $@"
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
