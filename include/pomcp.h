@@ -265,6 +265,32 @@ int pomcp_get_root_prior(pomcp_ctx* ctx, int32_t tree, double* out);
 int pomcp_get_root_policies(pomcp_ctx* ctx, int32_t tree, int32_t* out, int32_t capacity,
                             int32_t* count);
 
+/* Belief accuracy counts of every tree's current root belief, reduced on the
+ * device (k_belief_stats): what BeliefStatTracker (utils.py:147-339) needs of
+ * planner.root.belief without copying a particle to the host.
+ *   belief_size    planner.root.belief.size() (utils.py:227-228);
+ *   state_matches  particles whose state words (v0, v1) equal the tree's query
+ *                  state (get_state_accuracy, utils.py:292-297: hps.state ==
+ *                  state; the particle's t is not compared), -1 without states;
+ *   policy_hist[j] particles whose other-agent policy is index j (dict order of
+ *                  OtherAgentMixturePolicy.policies): the operand of
+ *                  get_other_policy_accuracy (utils.py:309-324) and
+ *                  get_other_action_accuracy (utils.py:326-339).  Type-based
+ *                  contexts only; zeros on plain contexts, whose particles
+ *                  carry no policy;
+ *   error          the tree's pomcp_status, or POMCP_E_INVALID if a particle's
+ *                  policy index is out of range (it is then in no bin). */
+typedef struct pomcp_belief_counts {
+  int32_t belief_size, state_matches, error, pad;
+  int32_t policy_hist[POMCP_MAX_TYPE_POLICIES];
+} pomcp_belief_counts;
+/* states: host [num_trees][2] (v0, v1) or NULL (state_matches = -1).  out: host
+ * [num_trees].  Runs on the context stream, after the update / search before
+ * it (a search leaves the root belief as it is).  POMCP_E_STATE before the
+ * first update (or pomcp_set_root_belief) after a reset, POMCP_E_INVALID on a
+ * null ctx / out; a tree's non-zero error is returned after `out` is filled. */
+int pomcp_belief_stats(pomcp_ctx* ctx, const uint32_t* states, pomcp_belief_counts* out);
+
 /* Arena use: the largest block count and particle-log record count over the
  * trees (after the last update's subtree compaction / the last search).  The
  * wall-clock loop sizes its chunks from it (never overflowing the arenas). */
@@ -389,6 +415,17 @@ int pomcp_philox_words(uint64_t seed, uint32_t tree, uint32_t stream, uint32_t f
  * planner's pomcp_config.log_table at C speed (wall-clock arenas ask for tens
  * of millions of entries). */
 int pomcp_host_log_table(int64_t first, int64_t n, double* out);
+
+/* ---- Host twin of pomcp_belief_stats ---------------------------------------
+ * The counts of one belief given as n host records {t, v0, v1, aux} (4 u32
+ * each), with the classification the kernel uses (csrc/belief_stats.h;
+ * utils.py:292-339).  state: the query (v0, v1) or NULL (state_matches = -1);
+ * num_other: 0 for a plain belief (aux is not read, the histogram stays
+ * zero), else the number of other-agent policies (1..8).  An aux >= num_other
+ * is counted in no bin: out is filled, out->error = POMCP_E_INVALID and that
+ * is returned (as for bad arguments, which leave out untouched). */
+int pomcp_host_belief_counts(const uint32_t* records4, int64_t n, const uint32_t* state,
+                             int32_t num_other, pomcp_belief_counts* out);
 
 #ifdef __cplusplus
 }

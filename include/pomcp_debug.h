@@ -50,6 +50,11 @@ int pomcp_debug_set_select_margin(pomcp_ctx* ctx, double rel);
 /* Only the first n (1..6) inline obs-child slots of each action node are used,
  * the overflow map holds the rest (tests of that path).  Before the first search. */
 int pomcp_debug_set_inline_slots(pomcp_ctx* ctx, int32_t n);
+/* Device time of k_belief_stats alone (pomcp_belief_stats without its copies):
+ * after one untimed launch, `reps` launches between two events on the context
+ * stream; *ms_per_launch = elapsed / reps.  states as pomcp_belief_stats. */
+int pomcp_debug_belief_stats_ms(pomcp_ctx* ctx, const uint32_t* states, int32_t reps,
+                                float* ms_per_launch);
 #ifdef __cplusplus
 }
 #endif

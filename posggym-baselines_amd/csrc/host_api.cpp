@@ -19,9 +19,11 @@
 #endif
 #include <stdint.h>
 
+#include <climits>
 #include <cmath>
 #include <cstring>
 
+#include "belief_stats.h"
 #include "driving.h"
 #include "host_exp.h"
 #include "philox.h"
@@ -114,6 +116,36 @@ int pomcp_host_log_table(int64_t first, int64_t n, double* out) {
     out[k] = i == 0 ? 0.0 : std::log((double)i);
   }
   return POMCP_OK;
+}
+
+// ---------------------------------------------------- host belief statistics
+
+// The counts k_belief_stats (belief_stats.hip) makes of one tree's root belief,
+// record by record with the same bel_classify (utils.py:292-339).
+int pomcp_host_belief_counts(const uint32_t* records4, int64_t n, const uint32_t* state,
+                             int32_t num_other, pomcp_belief_counts* out) {
+  if (!out || n < 0 || n > INT_MAX || (n > 0 && !records4) || num_other < 0 ||
+      num_other > POMCP_MAX_TYPE_POLICIES)
+    return POMCP_E_INVALID;
+  pomcp_belief_counts c;
+  std::memset(&c, 0, sizeof(c));
+  c.belief_size = (int32_t)n;
+  const int has_q = state != nullptr;
+  const uint32_t q0 = has_q ? state[0] : 0u, q1 = has_q ? state[1] : 0u;
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t* r = records4 + 4 * i;
+    // (a plain belief's aux word is not read)
+    const uint32_t k = bel_classify(r[1], r[2], num_other ? r[3] : 0u, q0, q1, has_q,
+                                    (uint32_t)num_other);
+    c.state_matches += (k & kBelMatch) ? 1 : 0;
+    if (k & kBelBadAux)
+      c.error = POMCP_E_INVALID;
+    else if (num_other)
+      c.policy_hist[k >> kBelPolShift] += 1;
+  }
+  if (!has_q) c.state_matches = -1;
+  *out = c;
+  return c.error;
 }
 
 // ---------------------------------------------------------- host PursuitEvasion

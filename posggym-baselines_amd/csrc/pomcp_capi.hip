@@ -19,6 +19,7 @@
 // the host-only entry points (environment models, RNG words, log / exp tables):
 // plain C++, also built on its own with the host sanitizers (tests/test_host_sanitize.py)
 #include "host_api.cpp"
+#include "belief_stats.hip"
 #include "pomcp_search.hip"
 #include "pomcp_search_lds.hip"
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
@@ -69,6 +70,11 @@ struct pomcp_ctx {
   bool lf_packed_cmap = true;   // POMCP_LF_PACKED_CMAP=off: tests only
   uint32_t lf_epoch = 0;
   int lf_grid = 0;
+  // some tree has had a root since the last reset (pomcp_update /
+  // pomcp_set_root_belief): pomcp_belief_stats has a belief to count
+  bool have_root = false;
+  pomcp_belief_counts* bel_out = nullptr;   // [B] device results of k_belief_stats
+  uint2* bel_q = nullptr;                   // [B] its query states
 };
 
 // Wave-per-tree search (k_search_lds) for batches up to this many trees: one
@@ -377,6 +383,7 @@ int pomcp_reset(pomcp_ctx* ctx) {
   HIP_TRY(ctx, hipGetLastError());
   ctx->have_snapshot = false;
   ctx->defer_pending = false;
+  ctx->have_root = false;
   return POMCP_OK;
 }
 
@@ -514,6 +521,7 @@ int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_key
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
   ctx->defer_pending = false;   // k_compact_log materialised the surviving deferred children
+  ctx->have_root = true;
   if (root_absorbing_out)
     for (int t = 0; t < B; ++t) root_absorbing_out[t] = ctx->host_upd[2 * t];
   return first_tree_error(ctx, ctx->host_upd.data(), 2, 1, "update");
@@ -690,6 +698,7 @@ int pomcp_set_root_belief(pomcp_ctx* ctx, int32_t tree, const uint32_t* particle
   HIP_TRY(ctx, hipMemcpyAsync(ctx->dp.hdr + tree, &h, sizeof(TreeHdr), hipMemcpyHostToDevice,
                               ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->have_root = true;
   return POMCP_OK;
 }
 
@@ -827,6 +836,60 @@ int pomcp_get_root_policies(pomcp_ctx* ctx, int32_t tree, int32_t* out, int32_t 
     if (rc != POMCP_OK) return rc;
   }
   for (int i = 0; i < n; ++i) out[i] = (int32_t)tmp[i].w;
+  return POMCP_OK;
+}
+
+// k_belief_stats on the context stream (belief_stats.hip): one workgroup per
+// tree, grid-strided beyond kBelMaxGrid; the query states are uploaded first
+// when given (upload = false: they are there already).  The results stay in
+// ctx->bel_out.
+static int launch_belief_stats(pomcp_ctx* ctx, const uint32_t* states, bool upload = true) {
+  const int B = ctx->dp.B;
+  if (!ctx->bel_out) {
+    void* p = nullptr;
+    int rc = dev_alloc(ctx, &p, sizeof(pomcp_belief_counts) * (size_t)B);
+    if (rc != POMCP_OK) return rc;
+    ctx->bel_out = reinterpret_cast<pomcp_belief_counts*>(p);
+    rc = dev_alloc(ctx, &p, sizeof(uint2) * (size_t)B);
+    if (rc != POMCP_OK) return rc;
+    ctx->bel_q = reinterpret_cast<uint2*>(p);
+  }
+  if (states && upload)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->bel_q, states, sizeof(uint2) * (size_t)B,
+                                hipMemcpyHostToDevice, ctx->stream));
+  const int num_other = ctx->dp.tm ? ctx->host_tm.n_other : 0;
+  hipLaunchKernelGGL(k_belief_stats, dim3((unsigned)(B < kBelMaxGrid ? B : kBelMaxGrid)),
+                     dim3(kBelThreads), 0, ctx->stream, ctx->dp,
+                     states ? (const uint2*)ctx->bel_q : (const uint2*)nullptr, num_other,
+                     ctx->bel_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return POMCP_OK;
+}
+
+static int belief_stats_ready(pomcp_ctx* ctx) {
+  if (ctx->dp.tm && !ctx->tm_set)
+    return fail(ctx, POMCP_E_STATE, "belief_stats: pomcp_set_type_policies first");
+  if (!ctx->have_root)
+    return fail(ctx, POMCP_E_STATE, "belief_stats: no root belief yet (update first)");
+  return POMCP_OK;
+}
+
+int pomcp_belief_stats(pomcp_ctx* ctx, const uint32_t* states, pomcp_belief_counts* out) {
+  if (!ctx || !out) return fail(ctx, POMCP_E_INVALID, "belief_stats: null argument");
+  int rc = belief_stats_ready(ctx);
+  if (rc != POMCP_OK) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = launch_belief_stats(ctx, states);
+  if (rc != POMCP_OK) return rc;
+  const int B = ctx->dp.B;
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->bel_out, sizeof(pomcp_belief_counts) * (size_t)B,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (int t = 0; t < B; ++t)
+    if (out[t].error != 0)
+      return fail(ctx, out[t].error, "belief_stats: tree " + std::to_string(t) + ": error " +
+                                         std::to_string(out[t].error) +
+                                         " (its own, or a particle's policy index out of range)");
   return POMCP_OK;
 }
 
@@ -1067,6 +1130,36 @@ int pomcp_debug_exp(const double* x, int32_t n, double* out) {
 // Debug: k_search's fast-selection margin (pomcp_debug.h); >= 1e-12 keeps
 // results exact, larger sends more selections to the exact FP64 scores
 // (counted in pomcp_root_stats.n_exact_selects).
+// Device time of k_belief_stats alone: `reps` launches between two events on the
+// context stream, after one untimed launch (tools/belief_stats_timing.py).
+int pomcp_debug_belief_stats_ms(pomcp_ctx* ctx, const uint32_t* states, int32_t reps,
+                                float* ms_per_launch) {
+  if (!ctx || !ms_per_launch || reps < 1) return POMCP_E_INVALID;
+  int rc = belief_stats_ready(ctx);
+  if (rc != POMCP_OK) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = launch_belief_stats(ctx, states);
+  if (rc != POMCP_OK) return rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIP_TRY(ctx, hipEventCreate(&e0));
+  hipError_t e = hipEventCreate(&e1);
+  if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
+  for (int32_t r = 0; r < reps && e == hipSuccess; ++r) {
+    rc = launch_belief_stats(ctx, states, false);
+    if (rc != POMCP_OK) break;
+  }
+  if (e == hipSuccess && rc == POMCP_OK) e = hipEventRecord(e1, ctx->stream);
+  if (e == hipSuccess && rc == POMCP_OK) e = hipEventSynchronize(e1);
+  float ms = 0.f;
+  if (e == hipSuccess && rc == POMCP_OK) e = hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (rc != POMCP_OK) return rc;
+  if (e != hipSuccess) return fail(ctx, POMCP_E_HIP, std::string("belief_stats_ms: ") + hipGetErrorString(e));
+  *ms_per_launch = ms / (float)reps;
+  return POMCP_OK;
+}
+
 int pomcp_debug_set_select_margin(pomcp_ctx* ctx, double rel) {
   if (!ctx || !(rel >= 1e-12) || !(rel <= 1.0)) return POMCP_E_INVALID;
   ctx->dp.sel_margin = rel;

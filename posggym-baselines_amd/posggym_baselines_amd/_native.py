@@ -163,6 +163,22 @@ class PomcpMergedRoot(C.Structure):
     ]
 
 
+class PomcpBeliefCounts(C.Structure):
+    """``pomcp_belief_counts`` (include/pomcp.h)."""
+    _fields_ = [
+        ("belief_size", C.c_int32),
+        ("state_matches", C.c_int32),
+        ("error", C.c_int32),
+        ("pad", C.c_int32),
+        ("policy_hist", C.c_int32 * POMCP_MAX_TYPE_POLICIES),
+    ]
+
+
+# the same record as a numpy dtype (PomcpEngine.belief_counts)
+BELIEF_COUNTS_DTYPE = [("belief_size", "<i4"), ("state_matches", "<i4"), ("error", "<i4"),
+                       ("pad", "<i4"), ("policy_hist", "<i4", (POMCP_MAX_TYPE_POLICIES,))]
+
+
 # (name, restype, argtypes) for every symbol include/pomcp.h declares.
 _CTX = C.c_void_p
 class PomcpTypePolicies(C.Structure):
@@ -206,6 +222,7 @@ SIGNATURES = [
     ("pomcp_set_type_policies", C.c_int, [_CTX, C.POINTER(PomcpTypePolicies)]),
     ("pomcp_get_root_prior", C.c_int, [_CTX, C.c_int32, _PD]),
     ("pomcp_get_root_policies", C.c_int, [_CTX, C.c_int32, _P32, C.c_int32, _P32]),
+    ("pomcp_belief_stats", C.c_int, [_CTX, _PU32, C.POINTER(PomcpBeliefCounts)]),
     ("pomcp_arena_usage", C.c_int, [_CTX, _P32, _P32]),
     ("pomcp_rekey", C.c_int, [_CTX, C.c_uint64]),
     ("pomcp_root_merge_buffer", C.c_int, [_CTX, C.POINTER(C.c_void_p)]),
@@ -228,6 +245,8 @@ SIGNATURES = [
     ("pomcp_philox_words", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
                                      _PU32]),
     ("pomcp_host_log_table", C.c_int, [C.c_int64, C.c_int64, _PD]),
+    ("pomcp_host_belief_counts", C.c_int,
+     [_PU32, C.c_int64, _PU32, C.c_int32, C.POINTER(PomcpBeliefCounts)]),
 ]
 DEBUG_SIGNATURES = [
     ("pomcp_debug_fp_selftest", C.c_int, [_PD, _PD, C.c_int32, _PD]),
@@ -239,6 +258,8 @@ DEBUG_SIGNATURES = [
     ("pomcp_debug_set_inline_slots", C.c_int, [C.c_void_p, C.c_int32]),
     ("pomcp_debug_set_select_margin", C.c_int, [C.c_void_p, C.c_double]),
     ("pomcp_debug_set_spin_limit", C.c_int, [C.c_void_p, C.c_int32]),
+    ("pomcp_debug_belief_stats_ms", C.c_int,
+     [C.c_void_p, _PU32, C.c_int32, C.POINTER(C.c_float)]),
     ("intmcp_debug_set_softmax_slack", C.c_int, [C.c_void_p, C.c_float]),
     ("intmcp_debug_exact_draws", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 ]

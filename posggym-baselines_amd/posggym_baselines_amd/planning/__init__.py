@@ -2,6 +2,7 @@
 the POMCP / I-NTMCP hot path on MI355X."""
 from posggym_baselines_amd.planning.config import MCTSConfig  # noqa: F401
 from posggym_baselines_amd.planning.episodes import (  # noqa: F401
+    EpisodeEnvView,
     EpisodeResultsWriter,
     run_planning_episodes,
 )
@@ -22,6 +23,7 @@ from posggym_baselines_amd.planning.search_policy import (  # noqa: F401
     load_posggym_agents_search_policy,
 )
 from posggym_baselines_amd.planning.utils import (  # noqa: F401
+    BeliefStatTracker,
     KnownBounds,
     MinMaxStats,
     PlanningStatTracker,

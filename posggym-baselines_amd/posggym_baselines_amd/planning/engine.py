@@ -367,6 +367,23 @@ class PomcpEngine:
             "get_root_belief")
         return buf[:3 * n.value].reshape(-1, 3)
 
+    def belief_counts(self, states=None):
+        """Belief accuracy counts of every tree's root belief, reduced on the
+        device (``pomcp_belief_stats``; utils.py:292-339): a structured array
+        [num_trees] of ``_native.BELIEF_COUNTS_DTYPE`` -- ``belief_size``,
+        ``state_matches`` against ``states`` ((v0, v1) per tree, or one pair for
+        every tree; -1 without), ``policy_hist`` (type-based engines) and
+        ``error``.  Raises if a tree reports an error."""
+        out = np.zeros(self.num_trees, dtype=N.BELIEF_COUNTS_DTYPE)
+        q = None
+        if states is not None:
+            s = np.ascontiguousarray(np.broadcast_to(
+                np.asarray(states, dtype=np.uint32).reshape(-1, 2), (self.num_trees, 2)))
+            q = s.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self._lib.pomcp_belief_stats(
+            self._ctx, q, out.ctypes.data_as(C.POINTER(N.PomcpBeliefCounts))), "belief_stats")
+        return out
+
     def set_root_belief(self, tree, rows):
         """Root belief of a fresh tree from host particles ((t, v0, v1) rows)."""
         a = np.ascontiguousarray(np.asarray(rows, dtype=np.uint32).reshape(-1, 3))

@@ -19,7 +19,12 @@ The non-planning agents are the experiments' uniform random policies
 ``ENV_TREE_KEY``), the stream the golden episodes were recorded with, so an
 episode here replays the reference planner's episode step for step
 (``tests/test_gpu_parity.py::test_episode_harness_replays_reference_episodes``).
-BeliefStatTracker columns (evaluation-only) are out of scope.
+
+With ``belief_tracker=BeliefStatTracker(planner, EpisodeEnvView(...), ...)`` the
+row also carries the tracker's ``belief_*_acc`` columns
+(``exp_utils.py:488-534``): the harness keeps the tracker's env view current
+(state, last observations, the other agents' last actions), resets the tracker
+after the planner and steps it after ``env_model.step``.
 """
 import csv
 import ctypes as C
@@ -32,6 +37,36 @@ from posggym_baselines_amd.planning.utils import PlanningStatTracker
 S_ENV_POLICY_BASE = 40   # philox.h S_ENV_POLICY_BASE: true agent i's random policy
 EPISODE_RESULT_HEADS = ["num", "len", "return", "discounted_return", "time"] + \
     PlanningStatTracker.STAT_KEYS
+
+
+class EpisodeEnvView:
+    """What ``BeliefStatTracker`` reads of the reference's ``AgentEnvWrapper``
+    (``utils.py:224-266``): ``state``, ``last_obs``, ``last_actions`` (the other
+    agents', ``None`` after a reset), ``policies[i].policy_id`` and ``spec``.
+    ``run_planning_episodes`` keeps it current.  ``policy_ids`` = {other agent:
+    the id its true policy goes by} (default: "uniform_random", what the
+    harness's other agents play)."""
+
+    def __init__(self, env_model, agent_id: str, policy_ids: Optional[Dict[str, str]] = None):
+        from types import SimpleNamespace
+        self.spec = env_model.spec
+        self.other_agent_ids = [i for i in env_model.possible_agents if i != agent_id]
+        ids = policy_ids or {}
+        self.policies = {i: SimpleNamespace(policy_id=ids.get(i, "uniform_random"))
+                         for i in self.other_agent_ids}
+        self.state = None
+        self.last_obs = {}
+        self.last_actions = {i: None for i in self.other_agent_ids}
+
+    def on_reset(self, state, obs):
+        self.state = state
+        self.last_obs = dict(obs)
+        self.last_actions = {i: None for i in self.other_agent_ids}
+
+    def on_step(self, state, obs, actions):
+        self.state = state
+        self.last_obs = dict(obs)
+        self.last_actions = {i: actions[i] for i in self.other_agent_ids}
 
 
 class UniformRandomAgents:
@@ -61,13 +96,15 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
                           env_seeds: Optional[List[int]] = None, discount: Optional[float] = None,
                           until: str = "agent_done", exp_time_limit: float = math.inf,
                           write_row: Optional[Callable[[Dict], None]] = None,
-                          on_step: Optional[Callable] = None) -> List[Dict]:
+                          on_step: Optional[Callable] = None,
+                          belief_tracker=None) -> List[Dict]:
     """Play ``num_episodes`` episodes of ``planner`` (agent ``agent_id``) in
     ``env_model`` against uniform random other agents; returns the result rows.
 
     ``env_seeds[e]`` seeds episode ``e``'s environment (model stream and the
     other agents' streams; default ``e``).  ``on_step(t, obs, actions, timestep)``
-    sees every step.
+    sees every step.  ``belief_tracker``: a ``BeliefStatTracker`` over an
+    ``EpisodeEnvView`` (its ``env``); its episode statistics join the row.
     """
     if until not in ("agent_done", "all_done"):
         raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
@@ -85,6 +122,9 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
         state = env_model.sample_initial_state()
         obs = env_model.sample_initial_obs(state)
         planner.reset()
+        if belief_tracker is not None:
+            belief_tracker.env.on_reset(state, obs)
+            belief_tracker.reset()
         res = {"num": num, "len": 0, "return": 0.0, "discounted_return": 0.0, "time": 0.0}
         t0 = time.time()
         done = False
@@ -102,6 +142,9 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
             res["discounted_return"] += gamma ** res["len"] * reward
             res["len"] += 1
             state, obs = ts.state, ts.observations
+            if belief_tracker is not None:
+                belief_tracker.env.on_step(state, obs, actions)
+                belief_tracker.step(belief_tracker.env)
             truncated = res["len"] >= limit
             if until == "agent_done":
                 done = ts.terminations[agent_id] or ts.truncations[agent_id] or ts.all_done
@@ -110,6 +153,8 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
             done = done or truncated
         res["time"] = time.time() - t0
         res.update(planner.stat_tracker.get_episode())
+        if belief_tracker is not None:
+            res.update(belief_tracker.get_episode())
         if write_row is not None:
             write_row(res)
         rows.append(res)
@@ -119,11 +164,14 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
 class EpisodeResultsWriter:
     """``episode_results.csv`` with the reference's header (``exp_utils.py:363-404``)."""
 
-    def __init__(self, path: str):
+    def __init__(self, path: str, extra_heads=()):
+        """``extra_heads``: further columns after the reference's, e.g.
+        ``BeliefStatTracker.get_stat_keys(...)``."""
         self.path = path
+        self.heads = EPISODE_RESULT_HEADS + list(extra_heads)
         with open(path, "w", newline="") as f:
-            csv.DictWriter(f, fieldnames=EPISODE_RESULT_HEADS).writeheader()
+            csv.DictWriter(f, fieldnames=self.heads).writeheader()
 
     def __call__(self, row: Dict):
         with open(self.path, "a", newline="") as f:
-            csv.DictWriter(f, fieldnames=EPISODE_RESULT_HEADS).writerow(row)
+            csv.DictWriter(f, fieldnames=self.heads).writerow(row)

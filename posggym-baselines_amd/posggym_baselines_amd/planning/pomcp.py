@@ -303,6 +303,86 @@ class POMCP:
         """Root particles as (t, v0, v1) packed u32 rows (of one replica)."""
         return self._engine.root_belief(replica)
 
+    # ------------------------------------------------------- belief accuracy
+    BELIEF_STATS = ("state", "policy", "action", "history")
+
+    def belief_stats(self, state=None, other_policy_ids=None, other_actions=None, *, stats=None):
+        """The root belief's accuracies (``BeliefStatTracker``, utils.py:292-339)
+        from per-tree counts reduced on the GPU (``pomcp_belief_stats``): no
+        particle leaves the device.
+
+        ``state``: the engine model's state, a (v0, v1) pair; ``other_policy_ids``
+        = {agent: true policy id}; ``other_actions`` = {agent: action just played}.
+        ``stats`` names the entries wanted (default: ``state`` / ``policy`` /
+        ``action`` for the arguments given, and ``history`` where it is defined).
+
+        * ``state``   matching particles / n (get_state_accuracy, 292-297);
+        * ``policy``  particles carrying the true policy id / n (309-324); 0.0
+          with ``state_belief_only`` (no policy state in the particles) or when
+          the id is not one of the mixture's;
+        * ``action``  (sum_j hist[j] * pi_j(a)) / n, pi_j from this planner's
+          ``other_agent_policies`` (326-339); 0.0 with ``state_belief_only``;
+        * ``history`` 0.0 with ``state_belief_only`` (299-307 skips particles
+          without a history); otherwise NotImplementedError: GPU particles carry
+          no joint history.
+        Every entry is 0.0 for an empty belief (227-228).  With ``root_parallel``
+        = K > 1 this rank's K replicas are pooled (summed counts / summed sizes).
+        """
+        sbo = bool(self.config.state_belief_only)
+        if stats is None:
+            stats = [k for k, given in (("state", state), ("policy", other_policy_ids),
+                                        ("action", other_actions)) if given is not None]
+            if sbo:
+                stats.append("history")
+        for k in stats:
+            if k not in self.BELIEF_STATS:
+                raise ValueError(f"unknown belief stat {k!r}")
+        if "history" in stats and not sbo:
+            raise NotImplementedError(
+                "belief history accuracy: the GPU particles carry no joint history "
+                "(defined here only with state_belief_only, where it is 0.0)")
+        if "state" in stats and state is None:
+            raise ValueError("belief stat 'state' needs the true state")
+        if "policy" in stats and other_policy_ids is None:
+            raise ValueError("belief stat 'policy' needs other_policy_ids")
+        if "action" in stats and other_actions is None:
+            raise ValueError("belief stat 'action' needs other_actions")
+        q = None
+        if "state" in stats:
+            q = [int(state[0]), int(state[1])]
+        counts = self._engine.belief_counts(q)
+        n = int(counts["belief_size"].sum(dtype=np.int64))
+        out = {k: 0.0 for k in stats}
+        if n == 0:
+            return out
+        if "state" in stats:
+            out["state"] = int(counts["state_matches"].sum(dtype=np.int64)) / n
+        if sbo or not ("policy" in stats or "action" in stats):
+            return out
+        others = [i for i in self.model.possible_agents if i != self.agent_id]
+        other = others[0]   # (the engine plans for two agents: base_type_tables)
+        pol = self.other_agent_policies[other]
+        mixture = getattr(pol, "policies", None)
+        if mixture is not None:
+            ids = list(mixture)
+            hist = [int(h) for h in counts["policy_hist"].sum(axis=0, dtype=np.int64)[:len(ids)]]
+            states = [{"policy_id": pid, "policy_state": mixture[pid].get_initial_state()}
+                      for pid in ids]
+        else:
+            # one stateless other-agent policy (policy state {}: no policy_id)
+            ids, hist, states = [None], [n], [pol.sample_initial_state()]
+        if "policy" in stats:
+            pid = other_policy_ids[other]
+            out["policy"] = hist[ids.index(pid)] / n if pid in ids else 0.0
+        if "action" in stats:
+            a = other_actions[other]
+            acc = 0.0
+            for j, s in enumerate(states):
+                if hist[j]:
+                    acc += hist[j] * pol.get_pi(s).get(a, 0.0)
+            out["action"] = acc / n
+        return out
+
     def close(self):
         self.search_policy.close()
         for p in self.other_agent_policies.values():
@@ -354,6 +434,12 @@ class BatchedPOMCP:
 
     def restore(self):
         self.engine.restore()
+
+    def belief_counts(self, states=None):
+        """Every tree's belief accuracy counts in one launch
+        (``PomcpEngine.belief_counts``): ``states`` is [num_trees][2] (v0, v1)
+        query states, or None for the sizes and policy histograms alone."""
+        return self.engine.belief_counts(states)
 
     def close(self):
         self.engine.close()

@@ -1,8 +1,9 @@
-"""Host-side planning utilities: ``KnownBounds``, ``MinMaxStats`` and the
+"""Host-side planning utilities: ``KnownBounds``, ``MinMaxStats``, the
 per-step statistics contract ``PlanningStatTracker``
-(``posggym_baselines/planning/utils.py:12-144``).  On the GPU the min/max
-statistics live in two registers per tree; this class is for host code that
-wants the same normalisation."""
+(``posggym_baselines/planning/utils.py:12-144``) and the belief accuracy
+tracker ``BeliefStatTracker`` (``utils.py:147-339``).  On the GPU the min/max
+statistics live in two registers per tree; ``MinMaxStats`` is for host code
+that wants the same normalisation."""
 from collections import namedtuple
 from typing import Dict, List, Optional
 
@@ -98,3 +99,146 @@ class PlanningStatTracker:
             out[f"{k}_mean"] = (np.nanmax if k in self.MAX_STATS else np.nanmean)(vals, axis=0)
             out[f"{k}_std"] = np.nanstd(vals, axis=0)
         return out
+
+
+class BeliefStatTracker:
+    """Accuracy of a planner's root belief per step / per episode
+    (``posggym_baselines/planning/utils.py:147-339``): ``policy`` (the other
+    agent's policy id), ``action`` (its action), ``state`` and ``history``.
+
+    The reference walks ``planner.root.belief.particles`` on the host; here each
+    ``step`` makes ONE ``planner.belief_stats`` call for all tracked statistics,
+    whose counts are reduced on the GPU (``pomcp_belief_stats``).  Same keys
+    (``belief_{k}_acc``, ``belief_{k}_acc_{t}``), NaN handling and bookkeeping:
+    the state / histories compared are those before the most recent action.
+
+    ``env`` is duck-typed: ``state`` (the engine model's (v0, v1) state),
+    ``last_obs``, ``last_actions`` ({other agent: action}, ``None`` values after
+    a reset), ``policies[i].policy_id`` and ``spec.max_episode_steps``.  Reset
+    it AFTER the environment has been reset, and call ``step`` after
+    ``planner.step`` and ``env.step``.
+
+    Not available for ``INTMCP`` planners (the reference reads ``planner.root``,
+    which for I-NTMCP is the episode's first root: no parity target), nor
+    ``history`` for planners whose particles carry joint histories
+    (``state_belief_only=False``): both raise ``NotImplementedError``.
+    """
+
+    TRACKABLE_BELIEF_STATS = ["policy", "action", "state", "history"]
+
+    def __init__(self, planner, env, track_per_step: bool = False,
+                 stats_to_track: List[str] = ["policy", "action", "state", "history"]):
+        from posggym_baselines_amd.planning.intmcp import INTMCP
+        from posggym_baselines_amd.planning.other_policy import OtherAgentPolicy
+        assert all(k in self.TRACKABLE_BELIEF_STATS for k in stats_to_track)
+        if isinstance(planner, INTMCP):
+            raise NotImplementedError("BeliefStatTracker is not defined for I-NTMCP planners")
+        if "history" in stats_to_track and not planner.config.state_belief_only:
+            raise NotImplementedError(
+                "belief history accuracy: the GPU particles carry no joint history "
+                "(track it only with state_belief_only=True, where it is 0.0)")
+        if any(k in stats_to_track for k in ["policy", "action"]):
+            assert all(isinstance(pi, OtherAgentPolicy)
+                       for pi in planner.other_agent_policies.values())
+        if track_per_step:
+            assert env.spec is not None
+            assert env.spec.max_episode_steps is not None
+            self.step_limit = env.spec.max_episode_steps
+        else:
+            self.step_limit = None
+        self.planner = planner
+        self.env = env
+        self.track_per_step = track_per_step
+        self.stats_to_track = stats_to_track
+        self.other_agent_ids = [i for i in planner.model.possible_agents if i != planner.agent_id]
+        self._current_steps = 0
+        self._current_state = None
+        self._current_other_agent_histories = {i: [(None, None)] for i in self.other_agent_ids}
+        self._num_episodes = 0
+        self._current_stats = {k: [] for k in self.stats_to_track}
+        self.reset()
+
+    @classmethod
+    def get_stat_keys(cls, stats_to_track: List[str], track_per_step: bool,
+                      step_limit: Optional[int]) -> List[str]:
+        assert all(k in cls.TRACKABLE_BELIEF_STATS for k in stats_to_track)
+        keys = []
+        for k in stats_to_track:
+            keys.append(f"belief_{k}_acc")
+            if track_per_step:
+                assert step_limit is not None
+                for t in range(step_limit):
+                    keys.append(f"belief_{k}_acc_{t}")
+        return keys
+
+    def _stats(self, stats, env=None, policies=None, actions=None, state=None):
+        """One ``planner.belief_stats`` call for ``stats`` (every value 0.0 for
+        an empty belief, utils.py:227-228)."""
+        env = self.env if env is None else env
+        kw = {}
+        if "state" in stats:
+            kw["state"] = state
+        if "policy" in stats:
+            policies = env.policies if policies is None else policies
+            kw["other_policy_ids"] = {i: policies[i].policy_id for i in self.other_agent_ids}
+        if "action" in stats:
+            actions = env.last_actions if actions is None else actions
+            kw["other_actions"] = {i: actions[i] for i in self.other_agent_ids}
+        return self.planner.belief_stats(stats=list(stats), **kw)
+
+    def step(self, env):
+        self._current_steps += 1
+        if self.stats_to_track:
+            # the belief's prediction of the actions just performed, of the state
+            # and the histories before the most recent action
+            vals = self._stats(self.stats_to_track, env, state=self._current_state)
+            for k in self.stats_to_track:
+                self._current_stats[k].append(vals[k])
+        for i, a in env.last_actions.items():
+            if i in self._current_other_agent_histories:
+                self._current_other_agent_histories[i].append((a, env.last_obs[i]))
+        self._current_state = env.state
+
+    def reset(self):
+        self.reset_episode()
+        self._num_episodes = 0
+
+    def reset_episode(self):
+        """At the beginning of each episode (after the environment's reset), or
+        after the final episode."""
+        assert all(a is None for a in self.env.last_actions.values()), \
+            "Must call reset environment before resetting BeliefStatTracker."
+        self._current_other_agent_histories = {
+            i: [(None, o)] for i, o in self.env.last_obs.items() if i in self.other_agent_ids}
+        self._current_state = self.env.state
+        if self._current_steps == 0:
+            return
+        self._num_episodes += 1
+        self._current_steps = 0
+        self._current_stats = {k: [] for k in self.stats_to_track}
+
+    def get_episode(self) -> Dict[str, float]:
+        stats = {}
+        for k, v in self._current_stats.items():
+            if len(v) == 0 or np.isnan(np.sum(v)):
+                v_mean = np.nan
+            else:
+                v_mean = np.nanmean(v, axis=0)
+            stats[f"belief_{k}_acc"] = v_mean
+            if self.track_per_step:
+                assert self.step_limit is not None
+                for t in range(self.step_limit):
+                    stats[f"belief_{k}_acc_{t}"] = np.nan if t >= len(v) else v[t]
+        return stats
+
+    def get_state_accuracy(self, state) -> float:
+        return self._stats(["state"], state=state)["state"]
+
+    def get_other_history_accuracy(self, histories=None) -> float:
+        return self._stats(["history"])["history"]
+
+    def get_other_policy_accuracy(self, policies) -> float:
+        return self._stats(["policy"], policies=policies)["policy"]
+
+    def get_other_action_accuracy(self, actions) -> float:
+        return self._stats(["action"], actions=actions)["action"]
