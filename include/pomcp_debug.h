@@ -55,6 +55,12 @@ int pomcp_debug_set_inline_slots(pomcp_ctx* ctx, int32_t n);
  * stream; *ms_per_launch = elapsed / reps.  states as pomcp_belief_stats. */
 int pomcp_debug_belief_stats_ms(pomcp_ctx* ctx, const uint32_t* states, int32_t reps,
                                 float* ms_per_launch);
+/* The compile-time depth limit of the tree-per-lane kernel (k_search) that the
+ * context's next search launch would use: its depth_limit when that is 1..3
+ * and the search is not type-based, else 0 = the generic kernel with a runtime
+ * limit (also when POMCP_SEARCH_DEPTH_SPEC=0 is set in the environment, or the
+ * launch goes to the wave-per-tree kernel).  Results are the same either way. */
+int pomcp_debug_search_depth_spec(const pomcp_ctx* ctx);
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,8 @@
 using namespace pb;
 
 // k_search lives in pomcp_search_tu.hip (a translation unit of its own)
-const void* pb_search_kernel(int row, int e, int sel);
+// (dl: its compile-time depth limit, the units of pomcp_search_dl_tu.hip; 0: the generic kernel)
+const void* pb_search_kernel(int row, int e, int sel, int dl);
 
 static_assert(sizeof(pomcp_grid) == sizeof(DrvGrid), "grid layout");
 static_assert(sizeof(pomcp_pe_grid) == 1344, "pe grid layout");
@@ -614,6 +615,22 @@ static int launch_search_wave(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   return POMCP_OK;
 }
 
+// The compile-time depth limit of the tree-per-lane kernel a launch uses
+// (k_search's DL, pomcp_search.hip): the context's own when a specialised
+// kernel exists for it, else 0, the generic kernel; POMCP_SEARCH_DEPTH_SPEC=0
+// forces the generic one (A/B runs and tests; results are the same).
+static int search_depth_spec(const pomcp_ctx* ctx) {
+  const char* f = std::getenv("POMCP_SEARCH_DEPTH_SPEC");
+  if (f != nullptr && f[0] == '0') return 0;
+  if (ctx->dp.tm || ctx->dp.depth_limit < 1 || ctx->dp.depth_limit > kRegPath) return 0;
+  return ctx->dp.depth_limit;
+}
+
+int pomcp_debug_search_depth_spec(const pomcp_ctx* ctx) {
+  if (!ctx) return POMCP_E_INVALID;
+  return resolve_search_kind(ctx) == POMCP_SEARCH_WAVE ? 0 : search_depth_spec(ctx);
+}
+
 static int launch_search(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   if (!ctx || num_sims < 0) return POMCP_E_INVALID;
   if (ctx->dp.tm && !ctx->tm_set) return fail(ctx, POMCP_E_STATE, "search: pomcp_set_type_policies first");
@@ -626,7 +643,8 @@ static int launch_search(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   const int row = (ctx->dp.tm ? 2 : 0) + (tpb == kTPB ? 0 : 1);
   int sims = (int)num_sims, fsel = final_sel;
   void* args[] = {&ctx->dp, &sims, &fsel};
-  HIP_TRY(ctx, hipLaunchKernel(pb_search_kernel(row, e, ctx->dp.sel), grid, block, args, 0, ctx->stream));
+  const int dl = search_depth_spec(ctx);
+  HIP_TRY(ctx, hipLaunchKernel(pb_search_kernel(row, e, ctx->dp.sel, dl), grid, block, args, 0, ctx->stream));
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->dp.defer && !ctx->dp.tm && num_sims > 0) ctx->defer_pending = true;
   return POMCP_OK;

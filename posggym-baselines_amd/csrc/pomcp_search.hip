@@ -119,9 +119,26 @@ enum : int { TP_LEVEL = 0, TP_ROLL = 1, TP_BACKUP = 2, TP_START = 3, TP_DONE = 4
 // policy, rollouts by the drawn ego policy; PUCB's prior is the node's
 // action_probs (a prior line per block), moved towards the drawn policy's
 // distribution on every arrival at an existing child (potmmcp.py:255-264).
-template <class Env, int SEL, int NA, int TPB, int TM>
+//
+// DL = 0: the depth limit is the runtime p.depth_limit (any value).
+// DL = 1..kRegPath: p.depth_limit == DL (the host checks, pomcp_capi.hip
+// launch_search) and the levels below the root are DL unrolled passes with a
+// compile-time depth: the register path and the backup queue have DL entries
+// written and read by constant index (no select chains over a runtime level
+// index, no p.path fallback), and the last pass -- always a cut-off level --
+// carries no child lookup when the cut-off records are deferred and no
+// expansion either way.  Results are those of DL = 0 bit for bit.
+template <int V>
+struct DepthC {   // a compile-time depth (0: the runtime one) as a lambda argument
+  static constexpr int value = V;
+};
+
+template <class Env, int SEL, int NA, int TPB, int TM, int DL = 0>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES_PER_EU, POMCP_WAVES_PER_EU))) void k_search(DevParams p, int num_sims, int final_sel) {
   static_assert(NA >= 2 && NA <= kMaxA, "action count");
+  static_assert(DL >= 0 && DL <= kRegPath && (DL == 0 || TM == 0), "depth specialisation");
+  constexpr int NR = DL > 0 ? DL : kRegPath;                  // register-path levels
+  constexpr int NQ = DL > 0 ? (DL < kBq ? DL : kBq) : kBq;    // queued backup levels
   __shared__ typename Env::Model sm;
   __shared__ uint4 rc[kRootParts][TPB];   // the root block of every lane's tree
   stage_model(p.model, sm);
@@ -552,7 +569,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 #pragma unroll
   for (int q = 0; q < kMaxA; ++q) rap[q] = 0.0;
   uint4 ppr[3] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-  PathEntry rpath[kRegPath];     // levels 1..kRegPath
+  PathEntry rpath[NR];           // levels 1..kRegPath (DL > 0: 1..DL)
   uint4 pre[kPre];               // node line of the next LEVEL pass's node (parts 0 .. A + 1)
 #pragma unroll
   for (int q = 0; q < kPre; ++q) pre[q] = make_uint4(0, 0, 0, 0);
@@ -572,16 +589,16 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   // level-1 node, can be it): its line is patched from the entry (fw_*) when
   // the level pass consumes it.  Queue entry l = path level l + 1.
   int q_n = 0;                      // queued levels (0..kBq)
-  int q_b[kBq];                     // block
-  uint32_t q_a[kBq];                // action
-  uint4 q_s1[kBq], q_vt[kBq];       // node line part 1 as written, {value, total}
-  uint32_t q_v[kBq];                // action a's visits (node line word a, a < 4)
+  int q_b[NQ];                      // block
+  uint32_t q_a[NQ];                 // action
+  uint4 q_s1[NQ], q_vt[NQ];         // node line part 1 as written, {value, total}
+  uint32_t q_v[NQ];                 // action a's visits (node line word a, a < 4)
   bool fw_on = false;               // the next level pass is depth 1: patch its line if fw_b
   int fw_b = -1;
   uint32_t fw_a = 0, fw_v = 0;
   uint4 fw_s1 = make_uint4(0, 0, 0, 0), fw_vt = make_uint4(0, 0, 0, 0);
 #pragma unroll
-  for (int l = 0; l < kBq; ++l) {
+  for (int l = 0; l < NQ; ++l) {
     q_b[l] = -1;
     q_a[l] = 0u;
     q_v[l] = 0u;
@@ -590,7 +607,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   }
   auto q_flush = [&]() {
 #pragma unroll
-    for (int l = 0; l < kBq; ++l) {
+    for (int l = 0; l < NQ; ++l) {
       if (l < q_n) {
         char* const lp = an + (int64_t)q_b[l] * blk_bytes;   // the node line
         if (q_a[l] < 4u) reinterpret_cast<uint32_t*>(lp)[q_a[l]] = q_v[l];
@@ -726,7 +743,15 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   // expand and roll out; else select there (next LEVEL).  cvis: the child's
   // visits with this arrival when it has no block (its slot's count); code:
   // its prior code (TM: the prior line of a block allocated for it).
-  auto descend = [&](int done, int cblk, int cvis, uint32_t n0, uint32_t n1, int code) {
+  // dn: the child's depth when it is a compile-time value (DL > 0), else 0.
+  auto descend = [&](auto dn, int done, int cblk, int cvis, uint32_t n0, uint32_t n1, int code) {
+    constexpr int DN = decltype(dn)::value;
+    if constexpr (DL > 0 && DN > DL) {   // beyond the depth limit whatever it holds: back up 0
+      ret = 0.0;
+      phase = TP_BACKUP;
+      depth += done ? 0 : 1;   // (search_depth)
+      return;
+    }
     if (done) {
       ret = 0.0;
       phase = TP_BACKUP;
@@ -737,7 +762,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     s1 = n1;
     ++t;
     ++depth;
-    if (depth > p.depth_limit || t > p.step_limit) {   // mcts.py:315
+    // mcts.py:315 (DL > 0: DN <= DL here)
+    if ((DL > 0 ? false : depth > p.depth_limit) || t > p.step_limit) {
       ret = 0.0;
       phase = TP_BACKUP;
     } else if (blk < 0) {                               // mcts.py:318-328
@@ -782,15 +808,21 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     const double ln = logtab((int)x.y + 2);
     *c1 = make_uint4(x.x, x.y + 1u, (uint32_t)__double2loint(ln), (uint32_t)__double2hiint(ln));
   };
-  auto push_path = [&](PathEntry pe) {
-    if (plen < kRegPath) {
-#pragma unroll
-      for (int l = 0; l < kRegPath; ++l)
-        if (plen == l) rpath[l] = pe;
+  auto push_path = [&](auto dc, PathEntry pe) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D > 0) {   // level D of an unrolled pass: its own registers
+      rpath[D - 1] = pe;
+      plen = D;
     } else {
-      path[plen] = pe;
+      if (plen < kRegPath) {
+#pragma unroll
+        for (int l = 0; l < kRegPath; ++l)
+          if (plen == l) rpath[l] = pe;
+      } else {
+        path[plen] = pe;
+      }
+      ++plen;
     }
-    ++plen;
   };
 
   // One iteration of this uniform loop = one simulation of every lane's tree,
@@ -921,19 +953,23 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
             r0_vis = sa.x;
             r0_r = r;
             r0_val = hilo_d(sa.z, sa.w);
-            descend(done, cblk, cvis, n0, n1, ccode);
+            descend(DepthC<(DL > 0 ? 1 : 0)>{}, done, cblk, cvis, n0, n1, ccode);
           }
         }
       }
       root_logn = logtab(root_visits + 1);   // the next simulation's (no wait)
       // the previous simulation's backup stores, after this one's first
       // node-line load (descend); entry 0 forwards to it
+      // (DL > 0: no copy -- the depth-1 pass reads entry 0 itself, which only
+      // the backup after it rewrites)
       fw_on = q_n > 0 && phase == TP_LEVEL;
-      fw_b = q_b[0];
-      fw_a = q_a[0];
-      fw_v = q_v[0];
-      fw_s1 = q_s1[0];
-      fw_vt = q_vt[0];
+      if constexpr (DL == 0) {
+        fw_b = q_b[0];
+        fw_a = q_a[0];
+        fw_v = q_v[0];
+        fw_s1 = q_s1[0];
+        fw_vt = q_vt[0];
+      }
       q_flush();
       PT_MARK(0);
     }
@@ -944,144 +980,31 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
       spec_blocks();
     }
     // ------------------------------------------------- the levels below the root
-    while (__ballot(phase == TP_LEVEL) != 0ull) {
-      if (phase == TP_LEVEL) {
-        const uint4* const ap = reinterpret_cast<const uint4*>(an + (int64_t)blk * blk_bytes);
-        const uint32_t j = take_mod(2);
-        const uint32_t ao = take_oth();
-        PT_MARK(8);
-        // the node line, prefetched by descend(): this arrival's N (its visits
-        // + 1) and math.log(N) are in it
-        if (fw_on) {   // the line loaded before the previous backup's stores (q_flush)
-          fw_on = false;
-          if (blk == fw_b) {
-            const uint32_t a4 = fw_a;
-            pre[0] = make_uint4(a4 == 0u ? fw_v : pre[0].x, a4 == 1u ? fw_v : pre[0].y,
-                                a4 == 2u ? fw_v : pre[0].z, a4 == 3u ? fw_v : pre[0].w);
-            pre[1] = fw_s1;
-#pragma unroll
-            for (int q = 2; q < kPre; ++q) pre[q] = sel4(q == part_vt((int)a4), fw_vt, pre[q]);
-          }
-        }
-        nvis = (int)pre[1].y + 1;
-        const double log_n = hilo_d(pre[1].z, pre[1].w);
-        const double lnx = logtab(nvis + 1);   // written back by the backup (no wait here)
-        uint4 st[kMaxA];   // {visits, -, value} per action, as select_action reads them
-  #pragma unroll
-        for (int q = 0; q < kMaxA; ++q)
-          st[q] = q < A ? make_uint4(line_visits(pre[0], pre[1], q), 0u, pre[part_vt(q)].x,
-                                     pre[part_vt(q)].y)
-                        : make_uint4(0, 0, 0, 0);
-        double lap[kMaxA];   // TM: the node's action_probs (its prior line)
-#pragma unroll
-        for (int q = 0; q < kMaxA; ++q)
-          lap[q] = TM != 0 ? hilo_d(q & 1 ? ppr[q >> 1].z : ppr[q >> 1].x, q & 1 ? ppr[q >> 1].w : ppr[q >> 1].y)
-                           : 0.0;
-        PT_MARK(1);
-        const int a = select_action(st, nvis, log_n, lap);
-        PT_MARK(2);
-        uint4 sa = st[0], va = pre[part_vt(0)];
-  #pragma unroll
-        for (int q = 1; q < kMaxA; ++q) {
-          sa = sel4(q == a, st[q], sa);
-          va = sel4(q == a, pre[part_vt(q < A ? q : 0)], va);
-        }
-        // the chosen action's child slots (second round trip) -- except for a
-        // child beyond the depth / step limits (mcts.py:315): the simulation
-        // stops there whatever its slot holds, so its record is deferred
-        // (pomcp_device.h: no slot read or write; the re-root materialises the
-        // children that survive it).  TM looks it up: the node's prior moves
-        // on arrivals at existing children (potmmcp.py:255-264).
-        // (p.defer = 0, pomcp_set_defer_cutoff: the eager lookup -- cheaper re-roots)
-        const bool cutc = depth + 1 > p.depth_limit || t + 1 > p.step_limit;   // mcts.py:315
-        c_cut += cutc ? 1 : 0;   // (stats: n_cutoff, and n_deferred when deferring)
-        const bool skipc = TM == 0 && p.defer && cutc;
-        uint4 sl[kSlots];
-  #pragma unroll
-        for (int q = 0; q < kSlots; ++q) sl[q] = make_uint4(0, 0, 0, 0);
-        if (!skipc) {
-  #pragma unroll
-          for (int q = 0; q < kSlots; ++q) sl[q] = ap[part_slot(a, q)];
-        }
-        PT_MARK(3);
-        append();   // the previous level's record, after this level's loads
-        uint32_t n0, n1;
-        double r;
-        int done;
-        uint64_t okey;
-        tree_step(a, ao, j, &n0, &n1, &r, &done, &okey, !skipc);
-        bool match = false;
-        int ks = 0;
-        if (!skipc) ks = find_slot(sl, okey, &match);
-        PT_MARK(12);
-        const uint32_t ani = (uint32_t)(blk * A + a);
-        uint32_t cid = 0;
-        int cblk = -1, cvis = 1, ccode = epol + 1, existed = 0;
-        leaf_rc = -1;
-        if (skipc) {
-          cid = p.cut_base + ani;
-        } else if (ks >= 0) {
-          uint4 sk = sl[0];
-  #pragma unroll
-          for (int q = 1; q < kSlots; ++q)
-            sk = sel4(q == ks, sl[q], sk);
-          cblk = match ? (int)sk.z : cblk;   // (selects, as at the root level)
-          cvis = match ? (int)sk.w + 1 : cvis;
-          n_nodes += match ? 0 : 1;
-          existed = match ? 1 : 0;
-          uint64_t nk = okey | kValidBit | ((uint64_t)done << 63);
-          if constexpr (TM != 0) {
-            ccode = match ? (int)((sk.y >> (kCodeShift - 32)) & 15u) : ccode;
-            nk |= (uint64_t)ccode << kCodeShift;
-          }
-          uint4* slot = const_cast<uint4*>(ap) + part_slot(a, ks);
-          // the slot changes beyond its visit count, or its count is needed
-          // (no block yet, within the limits): pomcp_device.h
-          const bool flip = (sk.y >> 31) != (uint32_t)done;
-          if (!match || flip || (cblk < 0 && (done || !cutc)))
-            *slot = make_uint4((uint32_t)nk, (uint32_t)(nk >> 32), (uint32_t)cblk, (uint32_t)cvis);
-          if (match && cblk >= 0 && done) bump_node(cblk);
-          cid = ani * kSlots + (uint32_t)ks + 1u;
-          leaf_ptr = reinterpret_cast<int32_t*>(slot) + 2;
-        } else {
-          const OvfChild o = ovf_child(ani, okey, done, cblk, cvis, ccode);
-          cid = o.cid;
-          cblk = o.cblk;
-          cvis = o.cvis;
-          ccode = o.code;
-          existed = o.existed;
-          leaf_ptr = o.cptr;
-          if (cblk >= 0 && done) bump_node(cblk);
-        }
-        if constexpr (TM != 0) {
-          if (existed) {   // this node's action_probs move (potmmcp.py:255-264)
-            prior_ema(lap, nvis);
-            double* const pl = reinterpret_cast<double*>(const_cast<uint4*>(ap) + part_prior(A));
-#pragma unroll
-            for (int q = 0; q < kMaxA; ++q)
-              if (q < A) pl[q] = lap[q];
-          }
-        }
-        PT_MARK(13);
-        if (err != 0 || n_log >= p.Np || plen >= kMaxPath) {
-          if (err == 0) err = POMCP_E_ARENA;
-          phase = TP_DONE;
-        } else {
-          rec = LogRec{cid | ((uint32_t)lane << kIdBits), n0, n1};   // mcts.py:371
-          app = true;
-          ++n_log;
-          const uint32_t ba = ((uint32_t)blk << 3) | (uint32_t)a;   // blk < 2^26 / 30
-          push_path(PathEntry{
-              make_uint4(ba | ((uint32_t)done << 31), sa.x, (uint32_t)__double2loint(r),
-                         (uint32_t)__double2hiint(r)),
-              va,
-              make_uint4(pre[1].x, (uint32_t)nvis, (uint32_t)__double2loint(lnx),
-                         (uint32_t)__double2hiint(lnx))});
-          PT_MARK(14);
-          descend(done, cblk, cvis, n0, n1, ccode);
-        }
-        PT_MARK(4);
+    // A pass is the text of pomcp_search_level.inc, with D = its compile-time
+    // depth (0: the runtime `depth`).  The unrolled passes go through one helper
+    // that takes D; the generic loop includes the text itself -- through the
+    // helper the inliner sees its lambdas in another order and the generic
+    // kernel's code changes (6 more AGPRs, -1.8% on the deep configuration).
+    auto level_pass = [&](auto dc) __attribute__((always_inline)) {
+      constexpr int D = decltype(dc)::value;
+      static_assert(D >= 1 && D <= DL, "unrolled passes: depths 1..DL");
+#include "pomcp_search_level.inc"
+    };
+    if constexpr (DL == 0) {
+      while (__ballot(phase == TP_LEVEL) != 0ull) {
+        constexpr int D = 0;
+        DepthC<0> dc;
+#include "pomcp_search_level.inc"
       }
+    } else {
+      if (__ballot(phase == TP_LEVEL) != 0ull) level_pass(DepthC<1>{});
+      if constexpr (DL >= 2) {
+        if (__ballot(phase == TP_LEVEL) != 0ull) level_pass(DepthC<2>{});
+      }
+      if constexpr (DL >= 3) {
+        if (__ballot(phase == TP_LEVEL) != 0ull) level_pass(DepthC<3>{});
+      }
+      static_assert(kRegPath == 3, "one unrolled pass per register-path level");
     }
     append();   // the last level's record
     // ------------------------------------------------------ the rollout
@@ -1126,7 +1049,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     if (phase == TP_BACKUP) {                                // mcts.py:374-381
       double gr = ret;
       // ql >= 0: a register-path level, its stores queued as entry ql
-      auto level = [&](const PathEntry& pe, int ql) {
+      // (DL > 0: qc = ql as a compile-time value, the entry written directly)
+      auto level = [&](auto qc, const PathEntry& pe, int ql) {
+        constexpr int QC = decltype(qc)::value;
         const uint4 e0 = pe.e0, e1 = pe.e1, e2 = pe.e2;
         const double r = hilo_d(e0.z, e0.w);
         gr = (e0.x >> 31) ? r : r + p.discount * gr;
@@ -1140,32 +1065,52 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
         const uint4 s1w = make_uint4(a == 4u ? (uint32_t)n : e2.x, e2.y, e2.z, e2.w);
         const uint4 vtw = make_uint4((uint32_t)__double2loint(value), (uint32_t)__double2hiint(value),
                                      (uint32_t)__double2loint(total), (uint32_t)__double2hiint(total));
-        if (ql < 0 || ql >= kBq) {
-          char* const lp = an + (int64_t)(ba >> 3) * blk_bytes;   // the node line
-          if (a < 4u) reinterpret_cast<uint32_t*>(lp)[a] = (uint32_t)n;
-          reinterpret_cast<uint4*>(lp)[1] = s1w;
-          reinterpret_cast<uint4*>(lp)[part_vt((int)a)] = vtw;
+        if constexpr (DL > 0 && QC < NQ) {
+          q_b[QC] = (int)(ba >> 3);
+          q_a[QC] = a;
+          q_v[QC] = (uint32_t)n;
+          q_s1[QC] = s1w;
+          q_vt[QC] = vtw;
         } else {
+          if (DL > 0 || ql < 0 || ql >= kBq) {
+            char* const lp = an + (int64_t)(ba >> 3) * blk_bytes;   // the node line
+            if (a < 4u) reinterpret_cast<uint32_t*>(lp)[a] = (uint32_t)n;
+            reinterpret_cast<uint4*>(lp)[1] = s1w;
+            reinterpret_cast<uint4*>(lp)[part_vt((int)a)] = vtw;
+          } else {
 #pragma unroll
-          for (int l = 0; l < kBq; ++l) {
-            if (l == ql) {
-              q_b[l] = (int)(ba >> 3);
-              q_a[l] = a;
-              q_v[l] = (uint32_t)n;
-              q_s1[l] = s1w;
-              q_vt[l] = vtw;
+            for (int l = 0; l < kBq; ++l) {
+              if (l == ql) {
+                q_b[l] = (int)(ba >> 3);
+                q_a[l] = a;
+                q_v[l] = (uint32_t)n;
+                q_s1[l] = s1w;
+                q_vt[l] = vtw;
+              }
             }
           }
         }
         if (value > mm_max) mm_max = value;   // utils.py:29-32
         if (value < mm_min) mm_min = value;
       };
-      for (int l = plen - 1; l >= kRegPath; --l) level(path[l], -1);
-      q_flush();   // (nothing queued: the START after the previous backup flushed)
+      if constexpr (DL > 0) {
+        // (no p.path levels; nothing is queued here: the START after the
+        // previous backup flushed)
+        if constexpr (DL >= 3) {
+          if (2 < plen) level(DepthC<2>{}, rpath[2], 2);
+        }
+        if constexpr (DL >= 2) {
+          if (1 < plen) level(DepthC<1>{}, rpath[1], 1);
+        }
+        if (0 < plen) level(DepthC<0>{}, rpath[0], 0);
+      } else {
+        for (int l = plen - 1; l >= kRegPath; --l) level(DepthC<-1>{}, path[l], -1);
+        q_flush();   // (nothing queued: the START after the previous backup flushed)
 #pragma unroll
-      for (int l = kRegPath - 1; l >= 0; --l)
-        if (l < plen) level(rpath[l], l);
-      q_n = plen < kBq ? plen : kBq;
+        for (int l = kRegPath - 1; l >= 0; --l)
+          if (l < plen) level(DepthC<-1>{}, rpath[l], l);
+      }
+      q_n = plen < NQ ? plen : NQ;
       if (lf_b >= 0) {   // the expanded leaf's own visits and log(N)
         reinterpret_cast<uint4*>(an + (int64_t)lf_b * blk_bytes)[1] =
             make_uint4(0u, lf_nv, (uint32_t)__double2loint(lf_ln), (uint32_t)__double2hiint(lf_ln));
@@ -1380,12 +1325,56 @@ PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall, 1)
 
 #endif  // PB_SEARCH_TU
 
+// The depth-specialised kernels (DL = PB_SEARCH_DL, TM = 0) are instantiated in
+// pomcp_search_dl_tu.hip, compiled once per DL (build.py).
+#ifdef PB_SEARCH_DL
+#define PB_SEARCH_INST(E, NA, T)                                                                   \
+  template __global__ void k_search<E, POMCP_SEL_PUCB, NA, T, 0, PB_SEARCH_DL>(DevParams, int, int);  \
+  template __global__ void k_search<E, POMCP_SEL_UCB, NA, T, 0, PB_SEARCH_DL>(DevParams, int, int);   \
+  template __global__ void k_search<E, POMCP_SEL_UNIFORM, NA, T, 0, PB_SEARCH_DL>(DevParams, int, int);
+PB_SEARCH_INST(EnvDriving, 5, kTPB)
+PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB)
+PB_SEARCH_INST(EnvDriving, 5, kTPBSmall)
+PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall)
+#undef PB_SEARCH_INST
+#endif  // PB_SEARCH_DL
+
 }  // namespace pb
 
+#ifdef PB_SEARCH_DL
+// The DL = PB_SEARCH_DL instantiation for (small workgroups, environment,
+// selection rule): pb_search_kernel below hands it on.
+#define PB_DL_CAT_(a, b) a##b
+#define PB_DL_CAT(a, b) PB_DL_CAT_(a, b)
+__attribute__((visibility("hidden"))) const void* PB_DL_CAT(pb_search_kernel_dl, PB_SEARCH_DL)(int small, int e,
+                                                                                              int sel) {
+  using namespace pb;
+  using KFn = void (*)(DevParams, int, int);
+#define PB_SEARCH_ROW(T)                                                  \
+  {{k_search<EnvDriving, POMCP_SEL_PUCB, 5, T, 0, PB_SEARCH_DL>,           \
+    k_search<EnvDriving, POMCP_SEL_UCB, 5, T, 0, PB_SEARCH_DL>,            \
+    k_search<EnvDriving, POMCP_SEL_UNIFORM, 5, T, 0, PB_SEARCH_DL>},       \
+   {k_search<EnvPursuitEvasion, POMCP_SEL_PUCB, 4, T, 0, PB_SEARCH_DL>,    \
+    k_search<EnvPursuitEvasion, POMCP_SEL_UCB, 4, T, 0, PB_SEARCH_DL>,     \
+    k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, 0, PB_SEARCH_DL>}}
+  static const KFn table[2][2][3] = {PB_SEARCH_ROW(kTPB), PB_SEARCH_ROW(kTPBSmall)};
+#undef PB_SEARCH_ROW
+  return reinterpret_cast<const void*>(table[small][e][sel]);
+}
+#endif  // PB_SEARCH_DL
+
 #ifdef PB_SEARCH_TU
+const void* pb_search_kernel_dl1(int small, int e, int sel);
+const void* pb_search_kernel_dl2(int small, int e, int sel);
+const void* pb_search_kernel_dl3(int small, int e, int sel);
 // The k_search instantiation launched for (row = 2 * TM + small workgroups,
-// environment, selection rule): pomcp_capi.hip launch_search.
-__attribute__((visibility("hidden"))) const void* pb_search_kernel(int row, int e, int sel) {
+// environment, selection rule, dl = its compile-time depth limit, 0 for the
+// generic kernel; TM = 0 only): pomcp_capi.hip launch_search.
+__attribute__((visibility("hidden"))) const void* pb_search_kernel(int row, int e, int sel, int dl) {
+  static_assert(pb::kRegPath == 3, "one depth-specialised unit per register-path level");
+  if (dl == 1) return pb_search_kernel_dl1(row & 1, e, sel);
+  if (dl == 2) return pb_search_kernel_dl2(row & 1, e, sel);
+  if (dl == 3) return pb_search_kernel_dl3(row & 1, e, sel);
   using namespace pb;
   using KFn = void (*)(DevParams, int, int);
 #define PB_SEARCH_ROW(T, TM)                                                                      \

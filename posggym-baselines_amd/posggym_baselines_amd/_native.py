@@ -260,6 +260,7 @@ DEBUG_SIGNATURES = [
     ("pomcp_debug_set_spin_limit", C.c_int, [C.c_void_p, C.c_int32]),
     ("pomcp_debug_belief_stats_ms", C.c_int,
      [C.c_void_p, _PU32, C.c_int32, C.POINTER(C.c_float)]),
+    ("pomcp_debug_search_depth_spec", C.c_int, [C.c_void_p]),
     ("intmcp_debug_set_softmax_slack", C.c_int, [C.c_void_p, C.c_float]),
     ("intmcp_debug_exact_draws", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 ]

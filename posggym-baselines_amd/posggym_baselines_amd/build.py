@@ -17,8 +17,11 @@ INCLUDE = os.path.join(REPO, "include")
 OUT = os.environ.get("POMCP_LIB_PATH") or os.path.join(PKG, "_lib", "libpomcp_hip.so")
 SOURCES = [os.path.join(CSRC, "pomcp_capi.hip")]
 SEARCH_SOURCE = os.path.join(CSRC, "pomcp_search_tu.hip")
-DEPS = SOURCES + [SEARCH_SOURCE] + [os.path.join(CSRC, f) for f in
-                  ("pomcp_kernels.hip", "pomcp_search.hip", "pomcp_search_lds.hip", "pomcp_device.h", "driving.h",
+# k_search specialised on depth limits 1..3 (pomcp_search.hip, DL): one object per limit
+SEARCH_DL_SOURCE = os.path.join(CSRC, "pomcp_search_dl_tu.hip")
+SEARCH_DLS = (1, 2, 3)
+DEPS = SOURCES + [SEARCH_SOURCE, SEARCH_DL_SOURCE] + [os.path.join(CSRC, f) for f in
+                  ("pomcp_kernels.hip", "pomcp_search.hip", "pomcp_search_level.inc", "pomcp_search_lds.hip", "pomcp_device.h", "driving.h",
                    "driving_vec.h", "philox.h", "envs.h", "pursuit_evasion.h", "host_exp.h", "host_exp_table.h", "host_api.cpp", "belief_stats.h", "belief_stats.hip", "intmcp.hip", "intmcp_capi.hip")] + [
     os.path.join(INCLUDE, "pomcp.h"), os.path.join(INCLUDE, "pomcp_debug.h"),
     os.path.join(INCLUDE, "intmcp.h")]
@@ -48,14 +51,16 @@ def build(force: bool = False, verbose: bool = True) -> str:
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     tmp = OUT + ".tmp"
-    objs = [tmp + ".capi.o", tmp + ".search.o"]
+    objs = [tmp + ".capi.o", tmp + ".search.o"] + [tmp + f".search_dl{d}.o" for d in SEARCH_DLS]
     cmds = [[HIPCC] + FLAGS + ["-c", "-o", objs[0]] + SOURCES,
             [HIPCC] + FLAGS + SEARCH_FLAGS + ["-c", "-o", objs[1], SEARCH_SOURCE]]
+    cmds += [[HIPCC] + FLAGS + SEARCH_FLAGS + [f"-DPB_SEARCH_DL={d}", "-c", "-o", o, SEARCH_DL_SOURCE]
+             for d, o in zip(SEARCH_DLS, objs[2:])]
     link = [HIPCC, f"--offload-arch={ARCH}", "-fPIC", "-shared", "-o", tmp] + objs
     if verbose:
         for c in cmds + [link]:
             print(" ".join(c), flush=True)
-    # the two units compile in parallel
+    # the units compile in parallel
     procs = [subprocess.Popen(c) for c in cmds]
     rcs = [p.wait() for p in procs]
     for c, rc in zip(cmds, rcs):

@@ -353,6 +353,11 @@ class PomcpEngine:
         """The kernel the next search uses: "lane" or "wave"."""
         return "wave" if self._lib.pomcp_search_kernel_used(self._ctx) == N.SEARCH_WAVE else "lane"
 
+    def search_depth_spec(self):
+        """The compile-time depth limit of the lane kernel the next search uses
+        (``pomcp_debug_search_depth_spec``): 1..3, or 0 for the generic kernel."""
+        return int(self._lib.pomcp_debug_search_depth_spec(self._ctx))
+
     def root_stats(self):
         self._check(self._lib.pomcp_get_root_stats(self._ctx, self._stats), "get_root_stats")
         return self._stats
