@@ -427,6 +427,108 @@ int pomcp_host_log_table(int64_t first, int64_t n, double* out);
 int pomcp_host_belief_counts(const uint32_t* records4, int64_t n, const uint32_t* state,
                              int32_t num_other, pomcp_belief_counts* out);
 
+/* ---- Batched episodes on the device (csrc/pomcp_episode.hip) ----------------
+ * One episode per tree, played without a host copy of any tree's state: the
+ * true environment state, the env streams' counters and the episode's result
+ * row live in device memory (run_planning_exp, baseline_exps/exp_utils.py:
+ * 468-552, for the whole batch; the other agent is uniform random,
+ * exp_utils.py:481).  A finished tree is parked: it is not searched, re-rooted
+ * or reinvigorated again and its record and last root statistics stay as they
+ * were, while its neighbours play on. */
+typedef enum pomcp_episode_until {
+  POMCP_UNTIL_AGENT_DONE = 0,   /* exp_utils.py:522: the planning agent is done */
+  POMCP_UNTIL_ALL_DONE = 1      /* tests/planning/test_pomcp.py:28: every agent is */
+} pomcp_episode_until;
+
+/* One tree's episode row (exp_utils.py:506-535) and planner statistics. */
+typedef struct pomcp_episode_result {
+  uint64_t env_seed;
+  int32_t len;                   /* environment steps played */
+  int32_t searched_steps;        /* steps that reached the planner's statistics: the root was
+                                    not absorbing before the step (mcts.py:97-117) */
+  double ret;                    /* sum of the ego's rewards, one FP64 add per step */
+  double discounted_return;      /* += pow_table[len] * reward, in step order */
+  int32_t ego_terminated, all_done, truncated;   /* after the last step played */
+  int32_t error;                 /* the tree's pomcp_status */
+  int64_t search_depth_sum;      /* over the searched steps */
+  int64_t num_sims_sum;
+  double min_value_sum;          /* sequential FP64 sums over the searched steps */
+  double max_value_sum;
+} pomcp_episode_result;
+
+/* One tree's whole episode record (device memory owned by the context; the
+ * host twin works on the same struct). */
+typedef struct pomcp_episode_state {
+  pomcp_episode_result res;
+  uint32_t v0, v1;               /* the true joint state */
+  uint32_t model_ctr;            /* env model stream: draws consumed */
+  uint32_t policy_ctr;           /* the other agent's policy stream: draws consumed */
+  int32_t last_action;           /* the ego's last action (-1 before the first step) */
+  int32_t finished;              /* by the `until` mode or truncation (or an error) */
+  int32_t root_absorbing;        /* the planner's root after the last step's update */
+  int32_t last_other_action;     /* the other agent's last action (-1 before the first step) */
+  double last_reward;            /* the ego's reward of the last step played */
+} pomcp_episode_state;
+
+/* What one step reads of the planner (the tree header and pomcp_root_stats). */
+typedef struct pomcp_episode_step_in {
+  int32_t root_absorbing;        /* the root after this step's update */
+  int32_t action;                /* pomcp_root_stats.action of this step's search */
+  int32_t search_depth, num_sims;
+  int32_t error, pad;
+  double min_value, max_value;
+} pomcp_episode_step_in;
+
+typedef struct pomcp_episode_step_out {
+  uint64_t obs_key;              /* the ego's next observation */
+  double reward;                 /* the ego's reward */
+  int32_t ego_action, other_action;
+  int32_t stepped, pad;          /* 0: the episode was finished already (nothing changed) */
+} pomcp_episode_step_out;
+
+/* pomcp_reset, then every tree's episode starts (k_episode_reset): tree b draws
+ * its initial state from the model stream under key (env_seeds[b], 0x40000000)
+ * as pomcp_driving_sample_initial_state / pomcp_pe_sample_initial_state do; the
+ * ego's initial observation and action -1 become the next update's inputs.
+ * pow_table: max_steps doubles, pow_table[t] = discount ** t as the host's
+ * Python computes it (the serial harness's `gamma ** len`, libm's pow).
+ * until: pomcp_episode_until. */
+int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
+                         int32_t max_steps, int32_t until);
+/* One episode step of every unfinished tree, with nothing per tree on the
+ * host: update from the device inputs (re-root unless this is the batch's first
+ * step), search with num_sims, k_episode_step (the environment's answer, the
+ * result row, the next update's inputs, finished trees parked).  live_out: the
+ * number of unfinished trees afterwards.  Tree errors surface as they do from
+ * pomcp_update / pomcp_search. */
+int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out);
+/* Every tree's row (host, [num_trees]). */
+int pomcp_episodes_results(pomcp_ctx* ctx, pomcp_episode_result* out);
+/* Every tree's whole record (host, [num_trees]): tests and diagnostics. */
+int pomcp_episodes_states(pomcp_ctx* ctx, pomcp_episode_state* out);
+/* on = 1: k_episode_reset / k_episode_step also write the true state the root
+ * belief is about -- the state before the step's joint action, (v0, v1) --
+ * into the query-state buffer of pomcp_belief_stats, and
+ * pomcp_episodes_belief_stats counts every root belief against it with no host
+ * copy of a state.  A finished tree keeps its last entry.  Takes effect at the
+ * next pomcp_episodes_begin. */
+int pomcp_episodes_track_states(pomcp_ctx* ctx, int32_t on);
+int pomcp_episodes_belief_stats(pomcp_ctx* ctx, pomcp_belief_counts* out);
+/* Device time (ms, events on the context stream) since pomcp_episodes_begin:
+ * ms[0] updates, ms[1] searches, ms[2] k_episode_step + the live count;
+ * *steps = pomcp_episodes_step calls. */
+int pomcp_episodes_timing(pomcp_ctx* ctx, double ms[3], int32_t* steps);
+
+/* ---- Host twin of the per-tree episode step (csrc/episode_step.h) ----------
+ * The code k_episode_reset / k_episode_step run per tree, on the host.
+ * grid: a pomcp_grid (env_id POMCP_ENV_DRIVING) or a pomcp_pe_grid. */
+int pomcp_host_episode_reset(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
+                             pomcp_episode_state* st, uint64_t* obs_key_out);
+int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
+                            const pomcp_episode_step_in* in, const double* pow_table,
+                            int32_t max_steps, int32_t until, pomcp_episode_state* st,
+                            pomcp_episode_step_out* out);
+
 #ifdef __cplusplus
 }
 #endif

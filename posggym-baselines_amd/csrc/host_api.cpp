@@ -25,6 +25,7 @@
 
 #include "belief_stats.h"
 #include "driving.h"
+#include "episode_step.h"
 #include "host_exp.h"
 #include "philox.h"
 #include "pursuit_evasion.h"
@@ -193,6 +194,50 @@ int pomcp_pe_obs(const pomcp_pe_grid* g, const uint32_t state[2], uint64_t obs_k
   return POMCP_OK;
 }
 
+// ------------------------------------------------------- host episode step
+
+// The per-tree work of k_episode_reset / k_episode_step (pomcp_episode.hip) on
+// the host, through the same episode_step.h.
+namespace {
+bool episode_env_ok(int32_t env_id, const void* grid, int32_t ego) {
+  return grid != nullptr && (ego == 0 || ego == 1) &&
+         (env_id == POMCP_ENV_DRIVING || env_id == POMCP_ENV_PURSUIT_EVASION);
+}
+}  // namespace
+
+int pomcp_host_episode_reset(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
+                             pomcp_episode_state* st, uint64_t* obs_key_out) {
+  if (!episode_env_ok(env_id, grid, ego) || !st || !obs_key_out) return POMCP_E_INVALID;
+  if (env_id == POMCP_ENV_DRIVING) {
+    DrvModel m;
+    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
+    *obs_key_out = episode_reset<EpDriving>(m, ego, env_seed, st);
+  } else {
+    PeModel m;
+    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
+    *obs_key_out = episode_reset<EpPursuitEvasion>(m, ego, env_seed, st);
+  }
+  return POMCP_OK;
+}
+
+int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
+                            const pomcp_episode_step_in* in, const double* pow_table,
+                            int32_t max_steps, int32_t until, pomcp_episode_state* st,
+                            pomcp_episode_step_out* out) {
+  if (!episode_env_ok(env_id, grid, ego) || !in || !pow_table || !st || !out || max_steps < 1 ||
+      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
+    return POMCP_E_INVALID;
+  if (env_id == POMCP_ENV_DRIVING) {
+    DrvModel m;
+    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
+    episode_step<EpDriving>(m, ego, *in, pow_table, max_steps, until, st, out);
+  } else {
+    PeModel m;
+    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
+    episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, st, out);
+  }
+  return POMCP_OK;
+}
 
 // Debug: the same host_exp on the host CPU (tests/test_host_exp.py compares it
 // with math.exp without a GPU).

@@ -20,6 +20,7 @@
 // plain C++, also built on its own with the host sanitizers (tests/test_host_sanitize.py)
 #include "host_api.cpp"
 #include "belief_stats.hip"
+#include "pomcp_episode.hip"
 #include "pomcp_search.hip"
 #include "pomcp_search_lds.hip"
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
@@ -76,6 +77,15 @@ struct pomcp_ctx {
   bool have_root = false;
   pomcp_belief_counts* bel_out = nullptr;   // [B] device results of k_belief_stats
   uint2* bel_q = nullptr;                   // [B] its query states
+  // batched episodes (pomcp_episodes_begin / _step): the device records, whether
+  // a batch is running, its steps so far, whether the true states are tracked
+  // in bel_q, and the device time of its phases (events on the stream)
+  EpDev ep{};
+  bool ep_active = false;
+  bool ep_track = false;
+  int32_t ep_steps = 0;
+  double ep_ms[3] = {0.0, 0.0, 0.0};
+  hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // Wave-per-tree search (k_search_lds) for batches up to this many trees: one
@@ -373,6 +383,8 @@ void pomcp_destroy(pomcp_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (void* p : ctx->allocs) (void)hipFree(p);
   if (ctx->snap_hdr) (void)hipFree(ctx->snap_hdr);
+  for (hipEvent_t e : ctx->ep_ev)
+    if (e) (void)hipEventDestroy(e);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -385,6 +397,7 @@ int pomcp_reset(pomcp_ctx* ctx) {
   ctx->have_snapshot = false;
   ctx->defer_pending = false;
   ctx->have_root = false;
+  ctx->ep_active = false;   // a batch of episodes ends with its trees
   return POMCP_OK;
 }
 
@@ -456,26 +469,18 @@ static int ensure_compaction_scratch(pomcp_ctx* ctx) {
   return POMCP_OK;
 }
 
-int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_keys,
-                 int32_t* root_absorbing_out) {
-  if (!ctx || !obs_keys) return POMCP_E_INVALID;
-  if (ctx->dp.tm && !ctx->tm_set) return fail(ctx, POMCP_E_STATE, "update: pomcp_set_type_policies first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+// The update's launches on inputs already in dp.in_actions / dp.in_obs
+// (pomcp_update uploads them; a batched episode step leaves them there).
+// reroot: some tree has an action (it is not the batch's initial update).
+// Asynchronous: the caller reads dp.upd_out / dp.lf_fail and synchronises.
+static int launch_update(pomcp_ctx* ctx, bool reroot) {
   const int B = ctx->dp.B;
-  std::vector<int32_t> acts((size_t)B, -1);
-  if (actions) std::memcpy(acts.data(), actions, sizeof(int32_t) * (size_t)B);
-  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_actions, acts.data(), sizeof(int32_t) * B,
-                              hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_obs, obs_keys, sizeof(uint64_t) * B,
-                              hipMemcpyHostToDevice, ctx->stream));
   // re-root: child lookup per tree; subtree compaction to the child's subtree
   // (re-roots only: an initial update leaves an empty arena) with one ordered
   // scan of each search wave's log that also extracts the child's particles;
   // then the per-tree update (initial belief / new root + reinvigoration)
   PB_ENV_LAUNCH(ctx, k_reroot_child, dim3(grid_blocks(B)), dim3(256), ctx->dp);
   HIP_TRY(ctx, hipGetLastError());
-  bool reroot = false;
-  for (int t = 0; t < B && !reroot; ++t) reroot = acts[t] >= 0;
   if (reroot) {
     int rc = ensure_compaction_scratch(ctx);
     if (rc != POMCP_OK) return rc;
@@ -513,6 +518,25 @@ int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_key
   }
   PB_ENV_LAUNCH(ctx, k_update, dim3(grid_blocks(B)), dim3(256), ctx->dp);
   HIP_TRY(ctx, hipGetLastError());
+  return POMCP_OK;
+}
+
+int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_keys,
+                 int32_t* root_absorbing_out) {
+  if (!ctx || !obs_keys) return POMCP_E_INVALID;
+  if (ctx->dp.tm && !ctx->tm_set) return fail(ctx, POMCP_E_STATE, "update: pomcp_set_type_policies first");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int B = ctx->dp.B;
+  std::vector<int32_t> acts((size_t)B, -1);
+  if (actions) std::memcpy(acts.data(), actions, sizeof(int32_t) * (size_t)B);
+  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_actions, acts.data(), sizeof(int32_t) * B,
+                              hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_obs, obs_keys, sizeof(uint64_t) * B,
+                              hipMemcpyHostToDevice, ctx->stream));
+  bool reroot = false;
+  for (int t = 0; t < B && !reroot; ++t) reroot = acts[t] >= 0;
+  const int rc = launch_update(ctx, reroot);
+  if (rc != POMCP_OK) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->host_upd.data(), ctx->dp.upd_out, sizeof(int32_t) * 2 * B,
                               hipMemcpyDeviceToHost, ctx->stream));
   uint32_t lf_fail = 0u;
@@ -1090,6 +1114,198 @@ int pomcp_restore(pomcp_ctx* ctx) {
                      ctx->snap_hdr);
   HIP_TRY(ctx, hipGetLastError());
   ctx->defer_pending = false;   // back to the post-update roots: no records left
+  return POMCP_OK;
+}
+
+// ------------------------------------------------------------ batched episodes
+
+#define PB_EP_LAUNCH(ctx, KERNEL, grid, ...)                                                    \
+  do {                                                                                           \
+    if ((ctx)->dp.env == POMCP_ENV_PURSUIT_EVASION)                                              \
+      hipLaunchKernelGGL(KERNEL<EpPursuitEvasion>, grid, dim3(kEpThreads), 0, (ctx)->stream,     \
+                         __VA_ARGS__);                                                           \
+    else                                                                                         \
+      hipLaunchKernelGGL(KERNEL<EpDriving>, grid, dim3(kEpThreads), 0, (ctx)->stream,            \
+                         __VA_ARGS__);                                                           \
+  } while (0)
+
+static unsigned episode_blocks(int B) { return (unsigned)((B + kEpThreads - 1) / kEpThreads); }
+
+// The query-state buffer of pomcp_belief_stats and its results (also allocated
+// by launch_belief_stats on its first use).
+static int ensure_belief_buffers(pomcp_ctx* ctx) {
+  if (ctx->bel_out) return POMCP_OK;
+  void* p = nullptr;
+  int rc = dev_alloc(ctx, &p, sizeof(pomcp_belief_counts) * (size_t)ctx->dp.B);
+  if (rc != POMCP_OK) return rc;
+  ctx->bel_out = reinterpret_cast<pomcp_belief_counts*>(p);
+  rc = dev_alloc(ctx, &p, sizeof(uint2) * (size_t)ctx->dp.B);
+  if (rc != POMCP_OK) return rc;
+  ctx->bel_q = reinterpret_cast<uint2*>(p);
+  return POMCP_OK;
+}
+
+int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
+                         int32_t max_steps, int32_t until) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!env_seeds || !pow_table || max_steps < 1 ||
+      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
+    return fail(ctx, POMCP_E_INVALID, "episodes_begin: bad arguments");
+  if (ctx->dp.tm && !ctx->tm_set)
+    return fail(ctx, POMCP_E_STATE, "episodes_begin: pomcp_set_type_policies first");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int B = ctx->dp.B;
+  EpDev& ep = ctx->ep;
+  int rc;
+  void* q = nullptr;
+  for (hipEvent_t& e : ctx->ep_ev)
+    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+  if (!ep.out) {   // (the last one allocated: a failed attempt is started over)
+    if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_episode_state) * (size_t)B)) != POMCP_OK) return rc;
+    ep.st = reinterpret_cast<pomcp_episode_state*>(q);
+    if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_root_stats) * (size_t)B)) != POMCP_OK) return rc;
+    ep.kept = reinterpret_cast<pomcp_root_stats*>(q);
+    if ((rc = dev_alloc(ctx, &q, sizeof(uint64_t) * (size_t)B)) != POMCP_OK) return rc;
+    ep.env_seeds = reinterpret_cast<const uint64_t*>(q);
+    if ((rc = dev_alloc(ctx, &q, sizeof(int32_t) * 2 * (size_t)episode_blocks(B))) != POMCP_OK)
+      return rc;
+    ep.part = reinterpret_cast<int32_t*>(q);
+    ep.in_actions = const_cast<int32_t*>(ctx->dp.in_actions);
+    ep.in_obs = const_cast<uint64_t*>(ctx->dp.in_obs);
+    if ((rc = dev_alloc(ctx, &q, sizeof(int32_t) * 2)) != POMCP_OK) return rc;
+    ep.out = reinterpret_cast<int32_t*>(q);
+  }
+  if (ep.pow_table == nullptr || ep.max_steps != max_steps) {
+    // (an earlier, shorter table stays allocated until the context goes)
+    if ((rc = dev_alloc(ctx, &q, sizeof(double) * (size_t)max_steps)) != POMCP_OK) return rc;
+    ep.pow_table = reinterpret_cast<const double*>(q);
+  }
+  ep.max_steps = max_steps;
+  ep.until = until;
+  ep.states = nullptr;
+  if (ctx->ep_track) {
+    if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
+    ep.states = ctx->bel_q;
+  }
+  ctx->ep_active = false;
+  if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint64_t*>(ep.env_seeds), env_seeds,
+                              sizeof(uint64_t) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(const_cast<double*>(ep.pow_table), pow_table,
+                              sizeof(double) * (size_t)max_steps, hipMemcpyHostToDevice,
+                              ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(ep.kept, 0, sizeof(pomcp_root_stats) * (size_t)B, ctx->stream));
+  PB_EP_LAUNCH(ctx, k_episode_reset, dim3(episode_blocks(B)), ctx->dp, ep);
+  HIP_TRY(ctx, hipGetLastError());
+  // the tables were copied from the caller's memory: finish before returning
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->ep_active = true;
+  ctx->ep_steps = 0;
+  ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
+  return POMCP_OK;
+}
+
+int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (num_sims < 0 || !live_out) return fail(ctx, POMCP_E_INVALID, "episodes_step: bad arguments");
+  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_step: pomcp_episodes_begin first");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int B = ctx->dp.B;
+  const bool reroot = ctx->ep_steps > 0;   // not the batch's first step
+  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[0], ctx->stream));
+  int rc = launch_update(ctx, reroot);
+  if (rc != POMCP_OK) return rc;
+  ctx->defer_pending = false;   // k_compact_log materialised the surviving deferred children
+  ctx->have_root = true;
+  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[1], ctx->stream));
+  if ((rc = launch_search(ctx, num_sims, 1)) != POMCP_OK) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[2], ctx->stream));
+  const unsigned nblk = episode_blocks(B);
+  PB_EP_LAUNCH(ctx, k_episode_step, dim3(nblk), ctx->dp, ctx->ep);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
+  int32_t counts[2] = {0, 0};
+  HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
+                              ctx->stream));
+  uint32_t lf_fail = 0u;
+  if (reroot && !ctx->log_scan_legacy)
+    HIP_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->ep_steps += 1;
+  for (int k = 0; k < 3; ++k) {
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
+    ctx->ep_ms[k] += (double)ms;
+  }
+  if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
+  *live_out = counts[0];
+  if (counts[1] != 0) {   // some tree failed: the update's error first, then the search's
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_upd.data(), ctx->dp.upd_out, sizeof(int32_t) * 2 * B,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    rc = first_tree_error(ctx, ctx->host_upd.data(), 2, 1, "update");
+    if (rc != POMCP_OK) return rc;
+    rc = pomcp_get_root_stats(ctx, ctx->host_stats.data());
+    if (rc != POMCP_OK) return rc;
+    return fail(ctx, POMCP_E_STATE, "episodes_step: an episode record reports an error");
+  }
+  return POMCP_OK;
+}
+
+int pomcp_episodes_states(pomcp_ctx* ctx, pomcp_episode_state* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_states: pomcp_episodes_begin first");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->ep.st, sizeof(pomcp_episode_state) * (size_t)ctx->dp.B,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_results(pomcp_ctx* ctx, pomcp_episode_result* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  std::vector<pomcp_episode_state> st((size_t)ctx->dp.B);
+  const int rc = pomcp_episodes_states(ctx, st.data());
+  if (rc != POMCP_OK) return rc;
+  for (int t = 0; t < ctx->dp.B; ++t) out[t] = st[t].res;
+  return POMCP_OK;
+}
+
+int pomcp_episodes_track_states(pomcp_ctx* ctx, int32_t on) {
+  if (!ctx || (on != 0 && on != 1)) return POMCP_E_INVALID;
+  ctx->ep_track = on != 0;   // from the next pomcp_episodes_begin on
+  return POMCP_OK;
+}
+
+int pomcp_episodes_belief_stats(pomcp_ctx* ctx, pomcp_belief_counts* out) {
+  if (!ctx || !out) return fail(ctx, POMCP_E_INVALID, "episodes_belief_stats: null argument");
+  if (!ctx->ep_active || ctx->ep.states == nullptr)
+    return fail(ctx, POMCP_E_STATE, "episodes_belief_stats: pomcp_episodes_track_states(1), then "
+                                    "pomcp_episodes_begin");
+  int rc = belief_stats_ready(ctx);
+  if (rc != POMCP_OK) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the query states are on the device already (k_episode_reset / k_episode_step)
+  rc = launch_belief_stats(ctx, reinterpret_cast<const uint32_t*>(ctx->bel_q), false);
+  if (rc != POMCP_OK) return rc;
+  const int B = ctx->dp.B;
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->bel_out, sizeof(pomcp_belief_counts) * (size_t)B,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (int t = 0; t < B; ++t)
+    if (out[t].error != 0)
+      return fail(ctx, out[t].error, "episodes_belief_stats: tree " + std::to_string(t) +
+                                         ": error " + std::to_string(out[t].error));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_timing(pomcp_ctx* ctx, double ms[3], int32_t* steps) {
+  if (!ctx || !ms || !steps) return POMCP_E_INVALID;
+  for (int k = 0; k < 3; ++k) ms[k] = ctx->ep_ms[k];
+  *steps = ctx->ep_steps;
   return POMCP_OK;
 }
 

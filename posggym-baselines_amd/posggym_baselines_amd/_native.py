@@ -179,6 +179,82 @@ BELIEF_COUNTS_DTYPE = [("belief_size", "<i4"), ("state_matches", "<i4"), ("error
                        ("pad", "<i4"), ("policy_hist", "<i4", (POMCP_MAX_TYPE_POLICIES,))]
 
 
+UNTIL_AGENT_DONE, UNTIL_ALL_DONE = 0, 1   # pomcp_episode_until
+
+
+class PomcpEpisodeResult(C.Structure):
+    """``pomcp_episode_result`` (include/pomcp.h)."""
+    _fields_ = [
+        ("env_seed", C.c_uint64),
+        ("len", C.c_int32),
+        ("searched_steps", C.c_int32),
+        ("ret", C.c_double),
+        ("discounted_return", C.c_double),
+        ("ego_terminated", C.c_int32),
+        ("all_done", C.c_int32),
+        ("truncated", C.c_int32),
+        ("error", C.c_int32),
+        ("search_depth_sum", C.c_int64),
+        ("num_sims_sum", C.c_int64),
+        ("min_value_sum", C.c_double),
+        ("max_value_sum", C.c_double),
+    ]
+
+
+class PomcpEpisodeState(C.Structure):
+    """``pomcp_episode_state`` (include/pomcp.h)."""
+    _fields_ = [
+        ("res", PomcpEpisodeResult),
+        ("v0", C.c_uint32),
+        ("v1", C.c_uint32),
+        ("model_ctr", C.c_uint32),
+        ("policy_ctr", C.c_uint32),
+        ("last_action", C.c_int32),
+        ("finished", C.c_int32),
+        ("root_absorbing", C.c_int32),
+        ("last_other_action", C.c_int32),
+        ("last_reward", C.c_double),
+    ]
+
+
+class PomcpEpisodeStepIn(C.Structure):
+    """``pomcp_episode_step_in`` (include/pomcp.h)."""
+    _fields_ = [
+        ("root_absorbing", C.c_int32),
+        ("action", C.c_int32),
+        ("search_depth", C.c_int32),
+        ("num_sims", C.c_int32),
+        ("error", C.c_int32),
+        ("pad", C.c_int32),
+        ("min_value", C.c_double),
+        ("max_value", C.c_double),
+    ]
+
+
+class PomcpEpisodeStepOut(C.Structure):
+    """``pomcp_episode_step_out`` (include/pomcp.h)."""
+    _fields_ = [
+        ("obs_key", C.c_uint64),
+        ("reward", C.c_double),
+        ("ego_action", C.c_int32),
+        ("other_action", C.c_int32),
+        ("stepped", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
+# the same records as numpy dtypes (BatchedPOMCP.run_episodes / episode_states)
+EPISODE_RESULT_DTYPE = [("env_seed", "<u8"), ("len", "<i4"), ("searched_steps", "<i4"),
+                        ("ret", "<f8"), ("discounted_return", "<f8"), ("ego_terminated", "<i4"),
+                        ("all_done", "<i4"), ("truncated", "<i4"), ("error", "<i4"),
+                        ("search_depth_sum", "<i8"), ("num_sims_sum", "<i8"),
+                        ("min_value_sum", "<f8"), ("max_value_sum", "<f8")]
+EPISODE_STATE_DTYPE = [("res", EPISODE_RESULT_DTYPE), ("v0", "<u4"), ("v1", "<u4"),
+                       ("model_ctr", "<u4"), ("policy_ctr", "<u4"), ("last_action", "<i4"),
+                       ("finished", "<i4"), ("root_absorbing", "<i4"),
+                       ("last_other_action", "<i4"), ("last_reward", "<f8")]
+
+
 # (name, restype, argtypes) for every symbol include/pomcp.h declares.
 _CTX = C.c_void_p
 class PomcpTypePolicies(C.Structure):
@@ -247,6 +323,18 @@ SIGNATURES = [
     ("pomcp_host_log_table", C.c_int, [C.c_int64, C.c_int64, _PD]),
     ("pomcp_host_belief_counts", C.c_int,
      [_PU32, C.c_int64, _PU32, C.c_int32, C.POINTER(PomcpBeliefCounts)]),
+    ("pomcp_episodes_begin", C.c_int, [_CTX, _PU64, _PD, C.c_int32, C.c_int32]),
+    ("pomcp_episodes_step", C.c_int, [_CTX, C.c_int32, _P32]),
+    ("pomcp_episodes_results", C.c_int, [_CTX, C.POINTER(PomcpEpisodeResult)]),
+    ("pomcp_episodes_states", C.c_int, [_CTX, C.POINTER(PomcpEpisodeState)]),
+    ("pomcp_episodes_track_states", C.c_int, [_CTX, C.c_int32]),
+    ("pomcp_episodes_belief_stats", C.c_int, [_CTX, C.POINTER(PomcpBeliefCounts)]),
+    ("pomcp_episodes_timing", C.c_int, [_CTX, _PD, _P32]),
+    ("pomcp_host_episode_reset", C.c_int,
+     [C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(PomcpEpisodeState), _PU64]),
+    ("pomcp_host_episode_step", C.c_int,
+     [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PomcpEpisodeStepIn), _PD, C.c_int32, C.c_int32,
+      C.POINTER(PomcpEpisodeState), C.POINTER(PomcpEpisodeStepOut)]),
 ]
 DEBUG_SIGNATURES = [
     ("pomcp_debug_fp_selftest", C.c_int, [_PD, _PD, C.c_int32, _PD]),

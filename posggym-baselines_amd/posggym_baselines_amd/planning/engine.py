@@ -456,6 +456,59 @@ class PomcpEngine:
             out.ctypes.data_as(C.POINTER(C.c_uint64))), "synthetic_step")
         return out
 
+    # ------------------------------------------------- batched episodes
+    def episodes_begin(self, env_seeds, pow_table, max_steps, until, track_states=False):
+        """Reset every tree and start one episode per tree on the device
+        (``pomcp_episodes_begin``); ``until`` is "agent_done" or "all_done"."""
+        seeds = np.ascontiguousarray(np.asarray(env_seeds, dtype=np.uint64).reshape(self.num_trees))
+        pw = np.ascontiguousarray(np.asarray(pow_table, dtype=np.float64))
+        if len(pw) < int(max_steps):
+            raise ValueError("pow_table needs max_steps entries")
+        mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
+        self._check(self._lib.pomcp_episodes_track_states(self._ctx, 1 if track_states else 0),
+                    "episodes_track_states")
+        self._check(self._lib.pomcp_episodes_begin(
+            self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+            pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_begin")
+
+    def episodes_step(self, num_sims):
+        """One step of every unfinished episode (``pomcp_episodes_step``); returns
+        the number of trees still playing."""
+        live = C.c_int32()
+        self._check(self._lib.pomcp_episodes_step(self._ctx, int(num_sims), C.byref(live)),
+                    "episodes_step")
+        return live.value
+
+    def episodes_results(self):
+        """Every tree's ``pomcp_episode_result`` as a structured array."""
+        out = np.zeros(self.num_trees, dtype=N.EPISODE_RESULT_DTYPE)
+        self._check(self._lib.pomcp_episodes_results(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeResult))), "episodes_results")
+        return out
+
+    def episodes_states(self):
+        """Every tree's whole ``pomcp_episode_state`` (tests and diagnostics)."""
+        out = np.zeros(self.num_trees, dtype=N.EPISODE_STATE_DTYPE)
+        self._check(self._lib.pomcp_episodes_states(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeState))), "episodes_states")
+        return out
+
+    def episodes_belief_counts(self):
+        """``belief_counts`` against the true states the episode kernels wrote on
+        the device (``episodes_begin(..., track_states=True)``)."""
+        out = np.zeros(self.num_trees, dtype=N.BELIEF_COUNTS_DTYPE)
+        self._check(self._lib.pomcp_episodes_belief_stats(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpBeliefCounts))), "episodes_belief_stats")
+        return out
+
+    def episodes_timing(self):
+        """Device milliseconds since ``episodes_begin`` spent in (updates,
+        searches, the episode step kernels), and the number of steps."""
+        ms = (C.c_double * 3)()
+        n = C.c_int32()
+        self._check(self._lib.pomcp_episodes_timing(self._ctx, ms, C.byref(n)), "episodes_timing")
+        return (ms[0], ms[1], ms[2]), n.value
+
     def snapshot(self):
         self._check(self._lib.pomcp_snapshot(self._ctx), "snapshot")
 

@@ -412,6 +412,9 @@ class BatchedPOMCP:
             step_limit = config.step_limit or model.spec.max_episode_steps
             capacities = plan_capacities(config, step_limit, num_sims, searches, reroot=reroot,
                                          num_actions=model.action_spaces[agent_id].n)
+            self._planned = (int(searches), bool(reroot))
+        else:
+            self._planned = None   # the caller's own capacities: not second-guessed
         self.num_trees = num_trees
         self.num_sims = num_sims
         self.engine = PomcpEngine(model, agent_id, config, num_trees=num_trees,
@@ -440,6 +443,108 @@ class BatchedPOMCP:
         (``PomcpEngine.belief_counts``): ``states`` is [num_trees][2] (v0, v1)
         query states, or None for the sizes and policy histograms alone."""
         return self.engine.belief_counts(states)
+
+    # ------------------------------------------------------------ episodes
+    def run_episodes(self, env_seeds=None, *, until: str = "agent_done",
+                     belief_states: bool = False, write_row=None, on_step=None):
+        """Play one episode per tree against uniform random other agents, the
+        whole batch in lockstep on the device; returns one result row per tree.
+
+        The batch's ``run_planning_episodes``: tree ``b`` plays the episode the
+        serial harness plays with planner key ``(seed, tree_key_base + b)`` and
+        environment seed ``env_seeds[b]`` (default ``b``) -- same actions,
+        rewards, length and returns, bit for bit.  Every step is one call
+        (``pomcp_episodes_step``: update from the device inputs, search,
+        ``k_episode_step``) and one integer comes back, the number of trees still
+        playing; a finished tree is parked while its neighbours play on.
+        ``until``: "agent_done" (the planning agent is done, exp_utils.py:522) or
+        "all_done" (every agent is); an episode is truncated at the model's
+        ``max_episode_steps``.  As with ``planner.reset()`` in the reference, the
+        planners' RNG streams are not reseeded between calls: a second call on
+        the same engine continues them (a fresh engine replays the first).
+
+        Row keys: ``EPISODE_RESULT_HEADS`` + ``env_seed``
+        (``EpisodeResultsWriter(path, extra_heads=["env_seed"])`` writes them).
+        ``num`` is the tree index.  ``time`` is the wall-clock time of this whole
+        call and ``search_time`` / ``update_time`` are the batch's device time per
+        step (mean over the steps): the BATCH's figures, the same in every row,
+        not a tree's share.  ``search_depth`` / ``num_sims`` / ``min_value`` /
+        ``max_value`` are the tree's means over the steps that reached the
+        planner's statistics (the root was not absorbing before the step, as
+        ``PlanningStatTracker`` sees them): integer sum / n, sequential FP64
+        sum / n; NaN for a tree without such a step.  ``mem_usage`` is the
+        process RSS (MiB); the other planner columns are 0.0.
+
+        ``belief_states``: the kernels also write each tree's true state (the one
+        its root belief is about) where ``episode_belief_counts()`` reads it, so
+        ``on_step`` can track belief accuracy with no host copy of a state.
+        ``write_row(row)`` is called per tree at the end; ``on_step(t, self)``
+        after every step (tests: ``episode_states()`` is the debug getter).
+        """
+        from posggym_baselines_amd.planning.episodes import EPISODE_RESULT_HEADS
+        if until not in ("agent_done", "all_done"):
+            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        B = self.num_trees
+        seeds = list(range(B)) if env_seeds is None else [int(s) for s in env_seeds]
+        if len(seeds) != B:
+            raise ValueError(f"env_seeds has {len(seeds)} entries for {B} trees")
+        spec = getattr(self.engine.model, "spec", None)
+        max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
+        if max_steps < 1:
+            raise ValueError("run_episodes needs the model's spec.max_episode_steps")
+        if self._planned is not None:
+            searches, reroot = self._planned
+            if not reroot or searches < max_steps:
+                raise ValueError(
+                    f"run_episodes re-roots up to {max_steps} times per tree: create the engine "
+                    f"with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one was "
+                    f"sized with searches={searches}, reroot={reroot})")
+        gamma = self.engine.config.discount
+        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
+        start = time.time()
+        self.engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states)
+        live, t = B, 0
+        while live > 0 and t < max_steps:
+            live = self.engine.episodes_step(self.num_sims)
+            if on_step is not None:
+                on_step(t, self)
+            t += 1
+        res = self.engine.episodes_results()
+        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
+        elapsed = time.time() - start
+        mem = psutil.Process().memory_info().rss / 1024**2
+        rows = []
+        for b in range(B):
+            r = res[b]
+            n = int(r["searched_steps"])
+            row = {k: 0.0 for k in EPISODE_RESULT_HEADS}
+            row.update(num=b, len=int(r["len"]), discounted_return=float(r["discounted_return"]),
+                       time=elapsed, env_seed=int(r["env_seed"]))
+            row["return"] = float(r["ret"])
+            if n == 0:
+                for k in EPISODE_RESULT_HEADS[5:]:
+                    row[k] = np.nan
+            else:
+                row.update(search_time=search_ms / 1e3 / steps, update_time=upd_ms / 1e3 / steps,
+                           search_depth=int(r["search_depth_sum"]) / n,
+                           num_sims=int(r["num_sims_sum"]) / n, mem_usage=mem,
+                           min_value=float(r["min_value_sum"]) / n,
+                           max_value=float(r["max_value_sum"]) / n)
+            if write_row is not None:
+                write_row(row)
+            rows.append(row)
+        return rows
+
+    def episode_states(self):
+        """Every tree's device episode record (``pomcp_episode_state``) as a
+        structured array: the true state, the stream counters, the last actions,
+        the flags and the result so far.  A debug getter."""
+        return self.engine.episodes_states()
+
+    def episode_belief_counts(self):
+        """``belief_counts`` against the true states ``run_episodes(...,
+        belief_states=True)`` keeps on the device."""
+        return self.engine.episodes_belief_counts()
 
     def close(self):
         self.engine.close()

@@ -1,0 +1,160 @@
+"""Time BatchedPOMCP.run_episodes against the host-stepped route it replaces.
+
+Driving-v1, full episodes (until every agent is done, truncated at 50 steps),
+one episode per tree on the same env seeds both ways:
+
+  * ``run_episodes``: one pomcp_episodes_step call per step (update from the
+    device inputs, search, k_episode_step), one integer back;
+  * the only route there was before: ``engine.update`` + ``engine.search`` per
+    step with every tree's environment stepped on the host through
+    ``DrivingModel.step`` (a ctypes call per tree and step) and the other
+    agent's action from ``UniformRandomAgents`` -- the loop lives here, not in
+    the package.  A tree whose episode ended is no longer stepped on the host;
+    its root is absorbing by then, so the update and the search leave it alone.
+
+Reported: wall time per episode step of each route (a host clock around calls
+that end in a stream synchronise; the whole batch is warmed up by one untimed
+run first), their ratio, and the device time of k_episode_step + the live count
+per step from events on the context stream (pomcp_episodes_timing).  The two
+routes' rows (length, return bits) must agree: exit status 1 if they do not.
+
+Usage (one GPU process, under its own time limit):
+
+    timeout -k 10 900 python tools/batched_episodes_timing.py \
+        --out profiles/batched_episodes_timing.json
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "posggym-baselines_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+CFG = dict(discount=0.95, search_time_limit=0.1, c=math.sqrt(2), truncated=False,
+           action_selection="ucb", pucb_exploration_fraction=0.25, known_bounds=None,
+           step_limit=None, epsilon=0.92, state_belief_only=True)
+
+
+def host_route(bp, seeds, num_sims, max_steps):
+    """Lockstep episodes with the environments on the host; returns
+    (rows [(len, return)], steps run, seconds)."""
+    import numpy as np
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning.episodes import UniformRandomAgents
+    B = len(seeds)
+    eng = bp.engine
+    models, others, states = [], [], []
+    keys = np.zeros(B, dtype=np.uint64)
+    for b, s in enumerate(seeds):
+        m = DrivingModel(seed=s)
+        o = UniformRandomAgents(m, s)
+        o.reset()
+        st = m.sample_initial_state()
+        keys[b] = m.obs_key(m.sample_initial_obs(st)["0"])
+        models.append(m)
+        others.append(o)
+        states.append(st)
+    t0 = time.perf_counter()
+    eng.reset()
+    last = np.full(B, -1, dtype=np.int32)
+    was_absorbing = np.zeros(B, dtype=bool)
+    done = np.zeros(B, dtype=bool)
+    lens = np.zeros(B, dtype=np.int64)
+    rets = [0.0] * B
+    steps = 0
+    while not done.all() and steps < max_steps:
+        absorbing = eng.update(last, keys)
+        actions = eng.search(num_sims)
+        for b in np.nonzero(~done)[0]:
+            m = models[b]
+            # planner.step: an absorbing root returns the last action (mcts.py:97-117)
+            a = int(last[b]) if was_absorbing[b] else int(actions[b])
+            ts = m.step(states[b], {"0": a, "1": others[b].act("1")})
+            states[b] = ts.state
+            keys[b] = m.obs_key(ts.observations["0"])
+            last[b] = a
+            rets[b] += ts.rewards["0"]
+            lens[b] += 1
+            done[b] = ts.all_done or lens[b] >= max_steps
+        was_absorbing = absorbing
+        steps += 1
+    sec = time.perf_counter() - t0
+    return [(int(lens[b]), float(rets[b]).hex()) for b in range(B)], steps, sec
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--trees", type=int, default=4096)
+    ap.add_argument("--sims", type=int, default=256)
+    ap.add_argument("--first-seed", type=int, default=3000)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default="-", help="JSON record path ('-': stdout only)")
+    args = ap.parse_args()
+
+    import torch
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
+
+    assert torch.cuda.is_available(), "this measurement needs the GPU"
+    B, S, dev = args.trees, args.sims, args.device
+    model = DrivingModel()
+    max_steps = model.spec.max_episode_steps
+    seeds = list(range(args.first_seed, args.first_seed + B))
+
+    def fresh():
+        # a new engine per run: the planners' RNG streams continue from episode to
+        # episode on one engine (MCTS.reset does not reseed), and the two routes
+        # must play the same episodes to be compared row by row
+        return BatchedPOMCP(model, "0", MCTSConfig(seed=0, num_sims=S, **CFG), B, S,
+                            searches=max_steps, reroot=True, device=dev)
+
+    bp = fresh()
+    try:
+        bp.run_episodes(seeds, until="all_done")   # warm-up: every kernel and shape of both routes
+    finally:
+        bp.close()
+    bp = fresh()
+    try:
+        t0 = time.perf_counter()
+        rows = bp.run_episodes(seeds, until="all_done")
+        dev_sec = time.perf_counter() - t0
+        (upd_ms, search_ms, step_ms), dev_steps = bp.engine.episodes_timing()
+    finally:
+        bp.close()
+    bp = fresh()
+    try:
+        host_rows, host_steps, host_sec = host_route(bp, seeds, S, max_steps)
+    finally:
+        bp.close()
+    agree = [(r["len"], float(r["return"]).hex()) for r in rows] == host_rows
+    dev_ms = dev_sec * 1e3 / dev_steps
+    host_ms = host_sec * 1e3 / host_steps
+    rec = {
+        "env": "Driving-v1", "trees": B, "sims": S, "until": "all_done",
+        "device": torch.cuda.get_device_name(dev),
+        "episode_steps_total": int(sum(r["len"] for r in rows)),
+        "run_episodes_steps": dev_steps, "run_episodes_s": dev_sec,
+        "run_episodes_ms_per_step": dev_ms,
+        "update_ms_per_step": upd_ms / dev_steps, "search_ms_per_step": search_ms / dev_steps,
+        "k_episode_step_ms_per_step": step_ms / dev_steps,
+        "host_route_steps": host_steps, "host_route_s": host_sec,
+        "host_route_ms_per_step": host_ms,
+        "host_over_run_episodes": host_ms / dev_ms,
+        "rows_agree": bool(agree),
+    }
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if args.out != "-":
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return 0 if agree else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
