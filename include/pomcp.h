@@ -432,7 +432,8 @@ int pomcp_host_belief_counts(const uint32_t* records4, int64_t n, const uint32_t
  * true environment state, the env streams' counters and the episode's result
  * row live in device memory (run_planning_exp, baseline_exps/exp_utils.py:
  * 468-552, for the whole batch; the other agent is uniform random,
- * exp_utils.py:481).  A finished tree is parked: it is not searched, re-rooted
+ * exp_utils.py:481, or drawn from a population: pomcp_episodes_set_population
+ * below).  A finished tree is parked: it is not searched, re-rooted
  * or reinvigorated again and its record and last root statistics stay as they
  * were, while its neighbours play on. */
 typedef enum pomcp_episode_until {
@@ -528,6 +529,85 @@ int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
                             const pomcp_episode_step_in* in, const double* pow_table,
                             int32_t max_steps, int32_t until, pomcp_episode_state* st,
                             pomcp_episode_step_out* out);
+
+/* ---- Batched episodes against a policy population (ABI 7, additive) ----------
+ * The other agent of every episode is drawn from a test population of fixed
+ * action distributions (UniformOtherAgentFn, utils/agent_env_wrapper.py:8-27:
+ * model.rng.choice(ids) at every reset; run_planning_exp,
+ * baseline_exps/exp_utils.py:468-552).  Tree b plays policy
+ *   uniform_int(word 0 of stream 44 under key (env_seeds[b], 0x40000000), num_policies)
+ * and that policy draws its action from word j of the other agent's policy
+ * stream (40 + agent) at its step j as CPython's random.choices does:
+ * bisect_right(cumulative(pi), word * 2^-32 * total, 0, A - 1). */
+typedef struct pomcp_episode_population {
+  int32_t num_policies;          /* 1..POMCP_MAX_TYPE_POLICIES */
+  int32_t pad;
+  double pi[POMCP_MAX_TYPE_POLICIES][POMCP_MAX_ACTIONS];   /* get_pi, action order */
+  /* index of the policy's id in the planner's OtherAgentMixturePolicy.policies
+   * (pomcp_type_policies.other_pi's order), -1: the planner does not model it */
+  int32_t mixture_index[POMCP_MAX_TYPE_POLICIES];
+} pomcp_episode_population;
+
+/* One tree's population record (a device array of its own, beside the
+ * pomcp_episode_state records). */
+typedef struct pomcp_episode_pop_state {
+  int32_t policy_index;          /* the episode's policy, -1 without a population */
+  int32_t mixture_index;         /* its pomcp_episode_population.mixture_index, else -1 */
+} pomcp_episode_pop_state;
+
+/* The population of the batches started by the following pomcp_episodes_begin
+ * calls (copied); NULL: back to the uniform random other agent. */
+int pomcp_episodes_set_population(pomcp_ctx* ctx, const pomcp_episode_population* pop);
+/* Every tree's population record (host, [num_trees]). */
+int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out);
+
+/* Belief accuracy accumulated on the device (k_episode_belief_acc): after
+ * k_episode_step, every tree that played this step adds the accuracies of its
+ * root belief (BeliefStatTracker.step, utils.py:147-339) to its record, in
+ * FP64 without contraction:
+ *   state   matches / n against the state before the joint action;
+ *   policy  hist[mixture_index of the tree's true policy] / n (0.0 for -1);
+ *   action  (sum over j ascending, hist[j] != 0, of hist[j] * other_pi[j][a]) / n
+ *           with a the other agent's action of this step and other_pi the
+ *           planner's pomcp_type_policies.other_pi;
+ * all 0.0 for an empty belief; policy and action 0.0 when the particles carry
+ * no policy (a plain context, or no_mixture_draw).  A parked tree is skipped
+ * without a particle of it being read: its record stays as it is. */
+typedef struct pomcp_episode_belief_acc {
+  double state_sum, policy_sum, action_sum;   /* sequential sums over the steps played */
+  int32_t count;                 /* steps recorded (= pomcp_episode_result.len) */
+  int32_t error;                 /* the tree's pomcp_status; POMCP_E_INVALID: a particle's
+                                    policy index out of range */
+} pomcp_episode_belief_acc;
+/* on = 1: from the next pomcp_episodes_begin on (implies
+ * pomcp_episodes_track_states); per_step = 1 also keeps every step's three
+ * values.  A record's error surfaces from pomcp_episodes_step. */
+int pomcp_episodes_track_belief_acc(pomcp_ctx* ctx, int32_t on, int32_t per_step);
+/* Every tree's record (host, [num_trees]). */
+int pomcp_episodes_belief_acc(pomcp_ctx* ctx, pomcp_episode_belief_acc* out);
+/* The per-step table (host, [num_trees][max_steps][3] doubles: state, policy,
+ * action; entries at t >= count are unspecified).  POMCP_E_STATE without per_step. */
+int pomcp_episodes_belief_acc_steps(pomcp_ctx* ctx, double* out);
+/* Device time (ms) of k_episode_belief_acc since pomcp_episodes_begin. */
+int pomcp_episodes_belief_acc_ms(pomcp_ctx* ctx, double* ms);
+
+/* Host twins: episode_step.h's population overloads (pop NULL: exactly
+ * pomcp_host_episode_reset / _step; ps may then be NULL) and the accuracy
+ * arithmetic k_episode_belief_acc does on a tree's counts (belief_stats.h
+ * bel_accuracy).  other_pi: the planner's [num_other][POMCP_MAX_ACTIONS] table
+ * (may be NULL when num_other = 0); out = {state, policy, action}. */
+int pomcp_host_episode_reset_pop(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
+                                 const pomcp_episode_population* pop, pomcp_episode_state* st,
+                                 pomcp_episode_pop_state* ps, uint64_t* obs_key_out);
+int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
+                                const pomcp_episode_step_in* in, const double* pow_table,
+                                int32_t max_steps, int32_t until,
+                                const pomcp_episode_population* pop,
+                                const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                                pomcp_episode_step_out* out);
+int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_index,
+                          int32_t other_action, const double* other_pi, int32_t num_other,
+                          double out[3]);
 
 #ifdef __cplusplus
 }

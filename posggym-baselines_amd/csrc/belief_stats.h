@@ -32,6 +32,42 @@ __host__ __device__ inline uint32_t bel_classify(uint32_t v0, uint32_t v1, uint3
   return c;
 }
 
+// The tracker's arithmetic on one belief's counts (POMCP.belief_stats,
+// planning/pomcp.py; utils.py:292-339): out = {state, policy, action}.
+//   n, matches, hist  the counts (hist: kBelAccPolicies bins);
+//   num_other         policies the particles carry (0: none -- policy and
+//                     action are 0.0);
+//   mixture_index     the true policy's bin, -1 (or out of range): not modelled;
+//   other_action      the action the other agent just played (< 0: none);
+//   other_pi          [num_other][pi_stride] the planner's get_pi tables.
+// Python's int / int and int * float on doubles: every integer here is exact
+// in a double, each quotient is one correctly rounded division, and the action
+// sum adds the non-zero bins' products in ascending order from 0.0 -- with
+// contraction off the same roundings as the host's, bit for bit.
+constexpr int kBelAccPolicies = 8;
+__host__ __device__ inline void bel_accuracy(int32_t n, int32_t matches, const int32_t* hist,
+                                             int32_t num_other, int32_t mixture_index,
+                                             int32_t other_action, const double* other_pi,
+                                             int32_t pi_stride, double out[3]) {
+#pragma clang fp contract(off)
+  out[0] = out[1] = out[2] = 0.0;
+  if (n <= 0) return;
+  const double dn = (double)n;
+  out[0] = (double)matches / dn;
+  if (num_other <= 0) return;
+  double pol = 0.0, acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < kBelAccPolicies; ++j) {
+    if (j >= num_other) continue;
+    const int32_t h = hist[j];
+    if (j == mixture_index) pol = (double)h / dn;
+    if (h != 0 && other_action >= 0 && other_action < pi_stride)
+      acc = acc + (double)h * other_pi[j * pi_stride + other_action];
+  }
+  out[1] = pol;
+  out[2] = acc / dn;
+}
+
 }  // namespace pb
 
 #endif  // PB_BELIEF_STATS_H_

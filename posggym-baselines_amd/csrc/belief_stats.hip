@@ -24,6 +24,58 @@ constexpr int kBelWords = 2 + kTmMax;   // matches, bad-aux flag, policy histogr
 static_assert(kTmMax == POMCP_MAX_TYPE_POLICIES, "histogram width");
 static_assert(sizeof(pomcp_belief_counts) == 4 * (4 + POMCP_MAX_TYPE_POLICIES), "counts layout");
 
+// The counts of the n records at `rec`, made by the whole workgroup: every
+// thread calls it with the same arguments; after its barrier red[w][] holds
+// wave w's counts ({matches, bad-aux flag, histogram}), which one thread adds up
+// with bel_totals.  The last group of a wave may be partial: its lanes past n
+// load nothing and classify as 0 (masked, not padded).  `red` is reused by the
+// next call: the caller puts a __syncthreads() between two calls.
+__device__ __forceinline__ void bel_count_block(const uint4* rec, int n, uint32_t q0, uint32_t q1,
+                                                int has_q, int num_other, int lane, int wave,
+                                                int32_t (*red)[kBelWords]) {
+  int32_t matches = 0, bad = 0;
+  int32_t hist[kTmMax];
+#pragma unroll
+  for (int j = 0; j < kTmMax; ++j) hist[j] = 0;
+  for (int64_t i0 = (int64_t)wave * kWave; i0 < n; i0 += kBelThreads) {
+    const int64_t i = i0 + lane;
+    const bool live = i < n;
+    uint32_t c = 0u;
+    if (live) {
+      const uint4 r = rec[i];
+      c = bel_classify(r.y, r.z, r.w, q0, q1, has_q, (uint32_t)num_other);
+    }
+    matches += (int32_t)__popcll(__ballot((c & kBelMatch) != 0u));
+    if (num_other > 0) {
+      bad |= __ballot((c & kBelBadAux) != 0u) != 0ull ? 1 : 0;
+      // a bad aux never reaches the histogram: its class is not counted
+      const bool ok = live && (c & kBelBadAux) == 0u;
+      const int pol = (int)(c >> kBelPolShift);
+#pragma unroll
+      for (int j = 0; j < kTmMax; ++j)
+        if (j < num_other) hist[j] += (int32_t)__popcll(__ballot(ok && pol == j));
+    }
+  }
+  if (lane == 0) {
+    red[wave][0] = matches;
+    red[wave][1] = bad;
+#pragma unroll
+    for (int j = 0; j < kTmMax; ++j) red[wave][2 + j] = hist[j];
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void bel_totals(const int32_t (*red)[kBelWords],
+                                           int32_t tot[kBelWords]) {
+#pragma unroll
+  for (int k = 0; k < kBelWords; ++k) {
+    int32_t t = 0;
+#pragma unroll
+    for (int w = 0; w < kBelWaves; ++w) t += red[w][k];
+    tot[k] = t;
+  }
+}
+
 // q: [B] query states (v0, v1), or null.  num_other: 0 on plain contexts (aux
 // is not looked at), else the number of other-agent policies.
 __global__ __launch_bounds__(kBelThreads) void k_belief_stats(DevParams dp, const uint2* q,
@@ -49,47 +101,10 @@ __global__ __launch_bounds__(kBelThreads) void k_belief_stats(DevParams dp, cons
       q0 = uniu(s.x);
       q1 = uniu(s.y);
     }
-    int32_t matches = 0, bad = 0;
-    int32_t hist[kTmMax];
-#pragma unroll
-    for (int j = 0; j < kTmMax; ++j) hist[j] = 0;
-    // the last group of a wave may be partial: its lanes past n load nothing
-    // and classify as 0 (masked, not padded)
-    for (int64_t i0 = (int64_t)wave * kWave; i0 < n; i0 += kBelThreads) {
-      const int64_t i = i0 + lane;
-      const bool live = i < n;
-      uint32_t c = 0u;
-      if (live) {
-        const uint4 r = rec[i];
-        c = bel_classify(r.y, r.z, r.w, q0, q1, has_q, (uint32_t)num_other);
-      }
-      matches += (int32_t)__popcll(__ballot((c & kBelMatch) != 0u));
-      if (num_other > 0) {
-        bad |= __ballot((c & kBelBadAux) != 0u) != 0ull ? 1 : 0;
-        // a bad aux never reaches the histogram: its class is not counted
-        const bool ok = live && (c & kBelBadAux) == 0u;
-        const int pol = (int)(c >> kBelPolShift);
-#pragma unroll
-        for (int j = 0; j < kTmMax; ++j)
-          if (j < num_other) hist[j] += (int32_t)__popcll(__ballot(ok && pol == j));
-      }
-    }
-    if (lane == 0) {
-      red[wave][0] = matches;
-      red[wave][1] = bad;
-#pragma unroll
-      for (int j = 0; j < kTmMax; ++j) red[wave][2 + j] = hist[j];
-    }
-    __syncthreads();
+    bel_count_block(rec, n, q0, q1, has_q, num_other, lane, wave, red);
     if (threadIdx.x == 0) {
       int32_t tot[kBelWords];
-#pragma unroll
-      for (int k = 0; k < kBelWords; ++k) {
-        int32_t s = 0;
-#pragma unroll
-        for (int w = 0; w < kBelWaves; ++w) s += red[w][k];
-        tot[k] = s;
-      }
+      bel_totals(red, tot);
       if (tot[1] != 0 && err == 0) err = POMCP_E_INVALID;
       int4* o = reinterpret_cast<int4*>(out + b);
       o[0] = make_int4(n, has_q ? tot[0] : -1, err, 0);

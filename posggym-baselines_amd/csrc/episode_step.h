@@ -2,8 +2,8 @@
 // 468-552, against a uniform random other agent): the start of an episode and
 // one environment step with its bookkeeping.  One implementation for the
 // device kernels (k_episode_reset / k_episode_step, pomcp_episode.hip) and
-// their host twins (pomcp_host_episode_reset / pomcp_host_episode_step,
-// host_api.cpp), so the CPU suite and the sanitized host build run the code
+// their host twins (pomcp_host_episode_reset / pomcp_host_episode_step and
+// their _pop forms, host_api.cpp), so the CPU suite and the sanitized host build run the code
 // the kernels run.  Plain C++: no HIP dependency.
 //
 // The environment's draws are those of the serial harness
@@ -12,6 +12,15 @@
 // execution-order shuffle (one draw per step, the counter carried from step to
 // step), and stream S_ENV_POLICY_BASE + i gives agent i's uniform action, one
 // draw per step.
+//
+// With a population (EpPopTables, from a pomcp_episode_population) the other
+// agent is one of its fixed-distribution policies instead: the reset draws the
+// episode's policy as uniform_int(word 0 of stream S_ENV_POPULATION, n) (the
+// build's model.rng.choice(ids), UniformOtherAgentFn,
+// utils/agent_env_wrapper.py:8-27) and the step turns the same word of the
+// agent's stream into an action as CPython's random.choices does
+// (PopulationAgents, planning/episodes.py).  A null population is the uniform
+// agent, draw for draw.
 #ifndef PB_EPISODE_STEP_H_
 #define PB_EPISODE_STEP_H_
 #include <stdint.h>
@@ -73,6 +82,47 @@ struct EpPursuitEvasion {
   }
 };
 
+// A population's draw tables: random.choices' cumulative weights
+// (itertools.accumulate) and total = cum[-1] + 0.0 per policy
+// (planning/policies.py cumulative), the doubles Python bisects.
+struct EpPopTables {
+  int32_t n, pad;
+  double cum[POMCP_MAX_TYPE_POLICIES][POMCP_MAX_ACTIONS];
+  double tot[POMCP_MAX_TYPE_POLICIES];
+  int32_t mix[POMCP_MAX_TYPE_POLICIES];
+};
+
+// false: not 1..8 policies, a negative (or NaN) probability, or a zero sum.
+inline bool ep_pop_tables(const pomcp_episode_population& p, int A, EpPopTables* t) {
+  if (p.num_policies < 1 || p.num_policies > POMCP_MAX_TYPE_POLICIES || A < 1 ||
+      A > POMCP_MAX_ACTIONS)
+    return false;
+  *t = EpPopTables{};
+  t->n = p.num_policies;
+  for (int k = 0; k < p.num_policies; ++k) {
+    double acc = 0.0;
+    for (int a = 0; a < A; ++a) {
+      if (!(p.pi[k][a] >= 0.0)) return false;
+      acc = a == 0 ? p.pi[k][a] : acc + p.pi[k][a];
+      t->cum[k][a] = acc;
+    }
+    t->tot[k] = acc + 0.0;
+    if (!(t->tot[k] > 0.0)) return false;
+    t->mix[k] = p.mixture_index[k];
+  }
+  return true;
+}
+
+// random.choices(range(n), weights): bisect_right(cum, x, 0, n - 1) for
+// x = random() * total (tm_choice of pomcp_device.h, for host and device).
+PB_HD int ep_choice(const double* cum, double total, int n, uint32_t w) {
+  const double x = uniform_float(w) * total;
+  int i = n - 1;
+  for (int q = n - 2; q >= 0; --q)
+    if (x < cum[q]) i = q;
+  return i;
+}
+
 PB_HD Streams episode_streams(const pomcp_episode_state& st) {
   Streams env;
   env.seed = st.res.env_seed;
@@ -113,13 +163,31 @@ PB_HD uint64_t episode_reset(const typename E::Model& m, int ego, uint64_t env_s
   return E::obs_key(m, ego, s.v0, s.v1);
 }
 
+// The same with a population (null: no draw, ps = {-1, -1}): the episode's
+// policy index and its mixture index go to *ps.
+template <class E>
+PB_HD uint64_t episode_reset(const typename E::Model& m, int ego, uint64_t env_seed,
+                             const EpPopTables* pop, pomcp_episode_state* st,
+                             pomcp_episode_pop_state* ps) {
+  pomcp_episode_pop_state r;
+  r.policy_index = r.mixture_index = -1;
+  if (pop != nullptr) {
+    r.policy_index = (int32_t)uniform_int(
+        philox_word(env_seed, kEnvTreeKey, (uint32_t)S_ENV_POPULATION, 0u), (uint32_t)pop->n);
+    r.mixture_index = pop->mix[r.policy_index];
+  }
+  *ps = r;
+  return episode_reset<E>(m, ego, env_seed, st);
+}
+
 // One step of an unfinished episode (out->stepped = 0 and nothing changes for a
 // finished one).  The planner's part is `in`; pow_table[t] = discount ** t has
 // max_steps entries.
+// pop / policy_index: the population and the episode's policy (null: uniform).
 template <class E>
 PB_HD void episode_step(const typename E::Model& m, int ego, const pomcp_episode_step_in& in,
-                        const double* pow_table, int max_steps, int until,
-                        pomcp_episode_state* st, pomcp_episode_step_out* out) {
+                        const double* pow_table, int max_steps, int until, const EpPopTables* pop,
+                        int policy_index, pomcp_episode_state* st, pomcp_episode_step_out* out) {
   pomcp_episode_state s = *st;
   out->obs_key = 0ull;
   out->reward = 0.0;
@@ -150,10 +218,16 @@ PB_HD void episode_step(const typename E::Model& m, int ego, const pomcp_episode
   s.root_absorbing = in.root_absorbing;
   // UniformRandomAgents.act (planning/episodes.py:85-92): draw j of the agent's stream
   const int other = 1 - ego;
-  const int a_oth = (int)uniform_int(
-      philox_word(s.res.env_seed, kEnvTreeKey, (uint32_t)S_ENV_POLICY_BASE + (uint32_t)other,
-                  s.policy_ctr),
-      E::kA);
+  // (PopulationAgents.act: the same word through the policy's bisection)
+  const uint32_t w_oth = philox_word(s.res.env_seed, kEnvTreeKey,
+                                     (uint32_t)S_ENV_POLICY_BASE + (uint32_t)other, s.policy_ctr);
+  int a_oth;
+  if (pop != nullptr) {
+    const int k = policy_index >= 0 && policy_index < pop->n ? policy_index : 0;
+    a_oth = ep_choice(pop->cum[k], pop->tot[k], (int)E::kA, w_oth);
+  } else {
+    a_oth = (int)uniform_int(w_oth, E::kA);
+  }
   s.policy_ctr += 1u;
   Streams env = episode_streams(s);
   uint32_t n0, n1;
@@ -185,6 +259,13 @@ PB_HD void episode_step(const typename E::Model& m, int ego, const pomcp_episode
   out->ego_action = a_ego;
   out->other_action = a_oth;
   out->stepped = 1;
+}
+
+template <class E>
+PB_HD void episode_step(const typename E::Model& m, int ego, const pomcp_episode_step_in& in,
+                        const double* pow_table, int max_steps, int until,
+                        pomcp_episode_state* st, pomcp_episode_step_out* out) {
+  episode_step<E>(m, ego, in, pow_table, max_steps, until, nullptr, -1, st, out);
 }
 
 }  // namespace pb

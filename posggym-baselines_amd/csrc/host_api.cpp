@@ -239,6 +239,78 @@ int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
   return POMCP_OK;
 }
 
+// The population overloads of episode_step.h (k_episode_reset / k_episode_step
+// with a population set); a null pop is the two entry points above.
+int pomcp_host_episode_reset_pop(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
+                                 const pomcp_episode_population* pop, pomcp_episode_state* st,
+                                 pomcp_episode_pop_state* ps, uint64_t* obs_key_out) {
+  if (!episode_env_ok(env_id, grid, ego) || !st || !obs_key_out) return POMCP_E_INVALID;
+  pomcp_episode_pop_state local;
+  if (!ps) {
+    if (pop) return POMCP_E_INVALID;
+    ps = &local;
+  }
+  EpPopTables t;
+  if (pop && !ep_pop_tables(*pop, env_id == POMCP_ENV_DRIVING ? (int)EpDriving::kA
+                                                              : (int)EpPursuitEvasion::kA, &t))
+    return POMCP_E_INVALID;
+  const EpPopTables* tp = pop ? &t : nullptr;
+  if (env_id == POMCP_ENV_DRIVING) {
+    DrvModel m;
+    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
+    *obs_key_out = episode_reset<EpDriving>(m, ego, env_seed, tp, st, ps);
+  } else {
+    PeModel m;
+    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
+    *obs_key_out = episode_reset<EpPursuitEvasion>(m, ego, env_seed, tp, st, ps);
+  }
+  return POMCP_OK;
+}
+
+int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
+                                const pomcp_episode_step_in* in, const double* pow_table,
+                                int32_t max_steps, int32_t until,
+                                const pomcp_episode_population* pop,
+                                const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                                pomcp_episode_step_out* out) {
+  if (!episode_env_ok(env_id, grid, ego) || !in || !pow_table || !st || !out || max_steps < 1 ||
+      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
+    return POMCP_E_INVALID;
+  EpPopTables t;
+  if (pop) {
+    if (!ps || !ep_pop_tables(*pop, env_id == POMCP_ENV_DRIVING ? (int)EpDriving::kA
+                                                                : (int)EpPursuitEvasion::kA, &t) ||
+        ps->policy_index < 0 || ps->policy_index >= t.n)
+      return POMCP_E_INVALID;
+  }
+  const EpPopTables* tp = pop ? &t : nullptr;
+  const int k = pop ? ps->policy_index : -1;
+  if (env_id == POMCP_ENV_DRIVING) {
+    DrvModel m;
+    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
+    episode_step<EpDriving>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
+  } else {
+    PeModel m;
+    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
+    episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
+  }
+  return POMCP_OK;
+}
+
+// The arithmetic k_episode_belief_acc does on a played tree's counts
+// (belief_stats.h bel_accuracy).
+int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_index,
+                          int32_t other_action, const double* other_pi, int32_t num_other,
+                          double out[3]) {
+  if (!counts || !out || num_other < 0 || num_other > POMCP_MAX_TYPE_POLICIES ||
+      (num_other > 0 && !other_pi) || counts->belief_size < 0)
+    return POMCP_E_INVALID;
+  bel_accuracy(counts->belief_size, counts->state_matches < 0 ? 0 : counts->state_matches,
+               counts->policy_hist, num_other, mixture_index, other_action, other_pi,
+               POMCP_MAX_ACTIONS, out);
+  return POMCP_OK;
+}
+
 // Debug: the same host_exp on the host CPU (tests/test_host_exp.py compares it
 // with math.exp without a GPU).
 int pomcp_debug_host_exp(const double* x, int32_t n, double* out) {

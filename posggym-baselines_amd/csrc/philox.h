@@ -36,6 +36,7 @@ enum Stream : uint32_t {
   S_ACT_BASE = 8, // Discrete.sample() of agent i: 8 + i
   S_ENV_MODEL = 32,
   S_ENV_POLICY_BASE = 40,
+  S_ENV_POPULATION = 44,  // harness: the episode's other-agent policy (model.rng.choice(ids))
 };
 
 // I-NTMCP: the middle planner of level l (1 <= l < the nesting level) draws its

@@ -21,6 +21,7 @@
 #include "host_api.cpp"
 #include "belief_stats.hip"
 #include "pomcp_episode.hip"
+#include "episode_belief_acc.hip"
 #include "pomcp_search.hip"
 #include "pomcp_search_lds.hip"
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
@@ -85,7 +86,23 @@ struct pomcp_ctx {
   bool ep_track = false;
   int32_t ep_steps = 0;
   double ep_ms[3] = {0.0, 0.0, 0.0};
-  hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // ([4], [5]: around k_episode_belief_acc)
+  hipEvent_t ep_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // the other agents' population (pomcp_episodes_set_population): the host's
+  // tables, their device copy, every tree's record
+  bool ep_pop_set = false;
+  EpPopTables host_pop{};
+  EpPopTables* dev_pop = nullptr;
+  pomcp_episode_pop_state* ep_ps = nullptr;   // [B]
+  // belief accuracy on the device (pomcp_episodes_track_belief_acc): what the
+  // next begin turns on, whether the running batch tracks, its device state
+  bool ep_acc_want = false, ep_acc_steps_want = false;
+  bool ep_acc = false;
+  EpAccDev acc{};
+  double* acc_steps_buf = nullptr;            // the per-step table and its capacity (doubles)
+  int64_t acc_steps_cap = 0;
+  double host_other_pi[kTmMax][POMCP_MAX_ACTIONS] = {};   // pomcp_type_policies.other_pi
+  double ep_acc_ms = 0.0;
 };
 
 // Wave-per-tree search (k_search_lds) for batches up to this many trees: one
@@ -831,6 +848,9 @@ int pomcp_set_type_policies(pomcp_ctx* ctx, const pomcp_type_policies* tp) {
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->host_tm = t;
+  std::memset(ctx->host_other_pi, 0, sizeof(ctx->host_other_pi));
+  for (int j = 0; j < no; ++j)
+    for (int a = 0; a < A; ++a) ctx->host_other_pi[j][a] = tp->other_pi[j][a];
   HIP_TRY(ctx, hipMemcpyAsync(const_cast<TmTables*>(ctx->dp.tmt), &ctx->host_tm, sizeof(TmTables),
                               hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1187,6 +1207,61 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
     ep.states = ctx->bel_q;
   }
+  if (!ctx->ep_ps) {
+    if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_episode_pop_state) * (size_t)B)) != POMCP_OK)
+      return rc;
+    ctx->ep_ps = reinterpret_cast<pomcp_episode_pop_state*>(q);
+  }
+  ep.ps = ctx->ep_ps;
+  ep.pop = nullptr;
+  if (ctx->ep_pop_set) {
+    if (!ctx->dev_pop) {
+      if ((rc = dev_alloc(ctx, &q, sizeof(EpPopTables))) != POMCP_OK) return rc;
+      ctx->dev_pop = reinterpret_cast<EpPopTables*>(q);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dev_pop, &ctx->host_pop, sizeof(EpPopTables),
+                                hipMemcpyHostToDevice, ctx->stream));
+    ep.pop = ctx->dev_pop;
+  }
+  ep.acc_part = nullptr;
+  ep.acc_nparts = 0;
+  ctx->ep_acc = false;
+  if (ctx->ep_acc_want) {
+    EpAccDev& acc = ctx->acc;
+    if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
+    ep.states = ctx->bel_q;
+    const int nparts = B < kBelMaxGrid ? B : kBelMaxGrid;
+    if (!acc.part) {   // (the last one allocated)
+      if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_episode_belief_acc) * (size_t)B)) != POMCP_OK)
+        return rc;
+      acc.rec = reinterpret_cast<pomcp_episode_belief_acc*>(q);
+      if ((rc = dev_alloc(ctx, &q, sizeof(ctx->host_other_pi))) != POMCP_OK) return rc;
+      acc.other_pi = reinterpret_cast<const double*>(q);
+      if ((rc = dev_alloc(ctx, &q, sizeof(int32_t) * (size_t)nparts)) != POMCP_OK) return rc;
+      acc.part = reinterpret_cast<int32_t*>(q);
+    }
+    const int64_t want = ctx->ep_acc_steps_want ? (int64_t)B * max_steps * 3 : 0;
+    if (want > ctx->acc_steps_cap) {
+      // (an earlier, smaller table stays allocated until the context goes)
+      if ((rc = dev_alloc(ctx, &q, sizeof(double) * (size_t)want)) != POMCP_OK) return rc;
+      ctx->acc_steps_cap = want;
+      ctx->acc_steps_buf = reinterpret_cast<double*>(q);
+    }
+    acc.steps = ctx->ep_acc_steps_want ? ctx->acc_steps_buf : nullptr;
+    acc.st = ep.st;
+    acc.ps = ctx->ep_ps;
+    acc.states = ctx->bel_q;
+    // particles carry a policy on a type-based context that draws one per particle
+    acc.num_other = ctx->dp.tm && !ctx->host_tm.no_mixture_draw ? ctx->host_tm.n_other : 0;
+    acc.max_steps = max_steps;
+    HIP_TRY(ctx, hipMemcpyAsync(const_cast<double*>(acc.other_pi), ctx->host_other_pi,
+                                sizeof(ctx->host_other_pi), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(acc.rec, 0, sizeof(pomcp_episode_belief_acc) * (size_t)B,
+                                ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(acc.part, 0, sizeof(int32_t) * (size_t)nparts, ctx->stream));
+    ep.acc_part = acc.part;
+    ep.acc_nparts = nparts;
+  }
   ctx->ep_active = false;
   if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint64_t*>(ep.env_seeds), env_seeds,
@@ -1202,6 +1277,8 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
   ctx->ep_active = true;
   ctx->ep_steps = 0;
   ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
+  ctx->ep_acc = ctx->ep_acc_want;
+  ctx->ep_acc_ms = 0.0;
   return POMCP_OK;
 }
 
@@ -1223,6 +1300,14 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
   const unsigned nblk = episode_blocks(B);
   PB_EP_LAUNCH(ctx, k_episode_step, dim3(nblk), ctx->dp, ctx->ep);
   HIP_TRY(ctx, hipGetLastError());
+  if (ctx->ep_acc) {
+    // the accuracies of the trees that played, against what k_episode_step wrote
+    HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[4], ctx->stream));
+    hipLaunchKernelGGL(k_episode_belief_acc, dim3((unsigned)ctx->ep.acc_nparts), dim3(kBelThreads),
+                       0, ctx->stream, ctx->dp, ctx->acc);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[5], ctx->stream));
+  }
   hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
@@ -1240,6 +1325,12 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
     ctx->ep_ms[k] += (double)ms;
   }
+  if (ctx->ep_acc) {   // its own figure, not a part of slot 2
+    float ms = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[4], ctx->ep_ev[5]));
+    ctx->ep_acc_ms += (double)ms;
+    ctx->ep_ms[2] -= (double)ms;
+  }
   if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
   *live_out = counts[0];
   if (counts[1] != 0) {   // some tree failed: the update's error first, then the search's
@@ -1250,6 +1341,18 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     if (rc != POMCP_OK) return rc;
     rc = pomcp_get_root_stats(ctx, ctx->host_stats.data());
     if (rc != POMCP_OK) return rc;
+    if (ctx->ep_acc) {
+      std::vector<pomcp_episode_belief_acc> rec((size_t)B);
+      HIP_TRY(ctx, hipMemcpyAsync(rec.data(), ctx->acc.rec, sizeof(rec[0]) * (size_t)B,
+                                  hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      for (int t = 0; t < B; ++t)
+        if (rec[t].error != 0)
+          return fail(ctx, rec[t].error, "episodes_step: belief accuracy of tree " +
+                                             std::to_string(t) + ": error " +
+                                             std::to_string(rec[t].error) +
+                                             " (its own, or a particle's policy index out of range)");
+    }
     return fail(ctx, POMCP_E_STATE, "episodes_step: an episode record reports an error");
   }
   return POMCP_OK;
@@ -1299,6 +1402,74 @@ int pomcp_episodes_belief_stats(pomcp_ctx* ctx, pomcp_belief_counts* out) {
     if (out[t].error != 0)
       return fail(ctx, out[t].error, "episodes_belief_stats: tree " + std::to_string(t) +
                                          ": error " + std::to_string(out[t].error));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_set_population(pomcp_ctx* ctx, const pomcp_episode_population* pop) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!pop) {
+    ctx->ep_pop_set = false;   // from the next pomcp_episodes_begin on
+    return POMCP_OK;
+  }
+  EpPopTables t;
+  if (!ep_pop_tables(*pop, ctx->dp.A, &t))
+    return fail(ctx, POMCP_E_INVALID, "episodes_set_population: 1..8 policies, probabilities >= 0 "
+                                      "with a positive sum");
+  for (int k = 0; k < t.n; ++k)
+    if (t.mix[k] < -1 || t.mix[k] >= kTmMax)
+      return fail(ctx, POMCP_E_INVALID, "episodes_set_population: mixture_index -1..7");
+  ctx->host_pop = t;
+  ctx->ep_pop_set = true;
+  return POMCP_OK;
+}
+
+int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active)
+    return fail(ctx, POMCP_E_STATE, "episodes_pop_states: pomcp_episodes_begin first");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->ep_ps, sizeof(pomcp_episode_pop_state) * (size_t)ctx->dp.B,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_track_belief_acc(pomcp_ctx* ctx, int32_t on, int32_t per_step) {
+  if (!ctx || (on != 0 && on != 1) || (per_step != 0 && per_step != 1)) return POMCP_E_INVALID;
+  ctx->ep_acc_want = on != 0;   // from the next pomcp_episodes_begin on
+  ctx->ep_acc_steps_want = on != 0 && per_step != 0;
+  return POMCP_OK;
+}
+
+int pomcp_episodes_belief_acc(pomcp_ctx* ctx, pomcp_episode_belief_acc* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active || !ctx->ep_acc)
+    return fail(ctx, POMCP_E_STATE, "episodes_belief_acc: pomcp_episodes_track_belief_acc(1, ..), "
+                                    "then pomcp_episodes_begin");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->acc.rec,
+                              sizeof(pomcp_episode_belief_acc) * (size_t)ctx->dp.B,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_belief_acc_steps(pomcp_ctx* ctx, double* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active || !ctx->ep_acc || ctx->acc.steps == nullptr)
+    return fail(ctx, POMCP_E_STATE, "episodes_belief_acc_steps: pomcp_episodes_track_belief_acc("
+                                    "1, 1), then pomcp_episodes_begin");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->acc.steps,
+                              sizeof(double) * 3 * (size_t)ctx->dp.B * (size_t)ctx->acc.max_steps,
+                              hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_belief_acc_ms(pomcp_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return POMCP_E_INVALID;
+  *ms = ctx->ep_acc_ms;
   return POMCP_OK;
 }
 

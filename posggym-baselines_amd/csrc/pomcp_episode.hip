@@ -8,10 +8,13 @@
 // episode_step, the code the host twins run.
 //
 // k_episode_reset  writes  ep.st[b] (cleared, initial state drawn), in_obs[b]
-//                  (the ego's initial observation), in_actions[b] = -1, and the
-//                  query state ep.states[b] when tracked.
+//                  (the ego's initial observation), in_actions[b] = -1, the
+//                  query state ep.states[b] when tracked, and ep.ps[b]: the
+//                  policy of the population (ep.pop) the tree's other agent
+//                  plays this episode, {-1, -1} without one.
 // k_episode_step   reads   hdr[b].root_abs / .error (after this step's update),
-//                  stats[b] (this step's search), ep.st[b], ep.pow_table;
+//                  stats[b] (this step's search), ep.st[b], ep.pow_table, and
+//                  with a population its tables and ep.ps[b].policy_index;
 //                  writes  ep.st[b], in_obs[b] / in_actions[b] (the next update's
 //                  inputs), ep.states[b] when tracked (the state before the
 //                  joint action: the one the root belief is about), and for a
@@ -47,6 +50,13 @@ struct EpDev {
   int32_t* part;                  // [workgroups][2] {unfinished, errors}
   int32_t* out;                   // [2] their sums
   int32_t max_steps, until;
+  // the other agents' population (pomcp_episodes_set_population): its draw
+  // tables, or null for the uniform agent, and every tree's record
+  const EpPopTables* pop;
+  pomcp_episode_pop_state* ps;    // [B], or null
+  // k_episode_belief_acc's error flags, one per workgroup (null: not tracking)
+  const int32_t* acc_part;
+  int32_t acc_nparts;
 };
 
 static_assert(sizeof(pomcp_episode_result) == 80, "episode result layout");
@@ -60,8 +70,10 @@ __global__ __launch_bounds__(kEpThreads) void k_episode_reset(DevParams p, EpDev
   const int b = (int)(blockIdx.x * kEpThreads + threadIdx.x);
   if (b >= p.B) return;
   pomcp_episode_state s;
-  const uint64_t key = episode_reset<E>(sm, p.ego, ep.env_seeds[b], &s);
+  pomcp_episode_pop_state r;
+  const uint64_t key = episode_reset<E>(sm, p.ego, ep.env_seeds[b], ep.pop, &s, &r);
   ep.st[b] = s;
+  if (ep.ps != nullptr) ep.ps[b] = r;
   ep.in_obs[b] = key;
   ep.in_actions[b] = -1;
   if (ep.states != nullptr) ep.states[b] = make_uint2(s.v0, s.v1);
@@ -98,7 +110,8 @@ __global__ __launch_bounds__(kEpThreads) void k_episode_step(DevParams p, EpDev 
         for (int k = 0; k < kW; ++k) ko[k] = so[k];
       const uint32_t q0 = s.v0, q1 = s.v1;
       pomcp_episode_step_out out;
-      episode_step<E>(sm, p.ego, in, ep.pow_table, ep.max_steps, ep.until, &s, &out);
+      episode_step<E>(sm, p.ego, in, ep.pow_table, ep.max_steps, ep.until, ep.pop,
+                      ep.pop != nullptr ? ep.ps[b].policy_index : -1, &s, &out);
       ep.st[b] = s;
       if (out.stepped) {
         ep.in_obs[b] = out.obs_key;
@@ -130,6 +143,8 @@ __global__ __launch_bounds__(kEpThreads) void k_episode_live(EpDev ep, int npart
     a += ep.part[2 * i];
     e += ep.part[2 * i + 1];
   }
+  if (ep.acc_part != nullptr)   // a belief accuracy record with an error counts as one
+    for (int i = (int)threadIdx.x; i < ep.acc_nparts; i += kEpThreads) e += ep.acc_part[i];
   red[0][threadIdx.x] = a;
   red[1][threadIdx.x] = e;
   __syncthreads();

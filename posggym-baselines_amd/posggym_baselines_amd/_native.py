@@ -243,6 +243,39 @@ class PomcpEpisodeStepOut(C.Structure):
     ]
 
 
+class PomcpEpisodePopulation(C.Structure):
+    """``pomcp_episode_population`` (include/pomcp.h)."""
+    _fields_ = [
+        ("num_policies", C.c_int32),
+        ("pad", C.c_int32),
+        ("pi", (C.c_double * POMCP_MAX_ACTIONS) * POMCP_MAX_TYPE_POLICIES),
+        ("mixture_index", C.c_int32 * POMCP_MAX_TYPE_POLICIES),
+    ]
+
+
+class PomcpEpisodePopState(C.Structure):
+    """``pomcp_episode_pop_state`` (include/pomcp.h)."""
+    _fields_ = [
+        ("policy_index", C.c_int32),
+        ("mixture_index", C.c_int32),
+    ]
+
+
+class PomcpEpisodeBeliefAcc(C.Structure):
+    """``pomcp_episode_belief_acc`` (include/pomcp.h)."""
+    _fields_ = [
+        ("state_sum", C.c_double),
+        ("policy_sum", C.c_double),
+        ("action_sum", C.c_double),
+        ("count", C.c_int32),
+        ("error", C.c_int32),
+    ]
+
+
+EPISODE_POP_STATE_DTYPE = [("policy_index", "<i4"), ("mixture_index", "<i4")]
+EPISODE_BELIEF_ACC_DTYPE = [("state_sum", "<f8"), ("policy_sum", "<f8"), ("action_sum", "<f8"),
+                            ("count", "<i4"), ("error", "<i4")]
+
 # the same records as numpy dtypes (BatchedPOMCP.run_episodes / episode_states)
 EPISODE_RESULT_DTYPE = [("env_seed", "<u8"), ("len", "<i4"), ("searched_steps", "<i4"),
                         ("ret", "<f8"), ("discounted_return", "<f8"), ("ego_terminated", "<i4"),
@@ -335,6 +368,21 @@ SIGNATURES = [
     ("pomcp_host_episode_step", C.c_int,
      [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PomcpEpisodeStepIn), _PD, C.c_int32, C.c_int32,
       C.POINTER(PomcpEpisodeState), C.POINTER(PomcpEpisodeStepOut)]),
+    ("pomcp_episodes_set_population", C.c_int, [_CTX, C.POINTER(PomcpEpisodePopulation)]),
+    ("pomcp_episodes_pop_states", C.c_int, [_CTX, C.POINTER(PomcpEpisodePopState)]),
+    ("pomcp_episodes_track_belief_acc", C.c_int, [_CTX, C.c_int32, C.c_int32]),
+    ("pomcp_episodes_belief_acc", C.c_int, [_CTX, C.POINTER(PomcpEpisodeBeliefAcc)]),
+    ("pomcp_episodes_belief_acc_steps", C.c_int, [_CTX, _PD]),
+    ("pomcp_episodes_belief_acc_ms", C.c_int, [_CTX, _PD]),
+    ("pomcp_host_episode_reset_pop", C.c_int,
+     [C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(PomcpEpisodePopulation),
+      C.POINTER(PomcpEpisodeState), C.POINTER(PomcpEpisodePopState), _PU64]),
+    ("pomcp_host_episode_step_pop", C.c_int,
+     [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PomcpEpisodeStepIn), _PD, C.c_int32, C.c_int32,
+      C.POINTER(PomcpEpisodePopulation), C.POINTER(PomcpEpisodePopState),
+      C.POINTER(PomcpEpisodeState), C.POINTER(PomcpEpisodeStepOut)]),
+    ("pomcp_host_belief_acc", C.c_int,
+     [C.POINTER(PomcpBeliefCounts), C.c_int32, C.c_int32, _PD, C.c_int32, _PD]),
 ]
 DEBUG_SIGNATURES = [
     ("pomcp_debug_fp_selftest", C.c_int, [_PD, _PD, C.c_int32, _PD]),

@@ -4,6 +4,7 @@ from posggym_baselines_amd.planning.config import MCTSConfig  # noqa: F401
 from posggym_baselines_amd.planning.episodes import (  # noqa: F401
     EpisodeEnvView,
     EpisodeResultsWriter,
+    PopulationAgents,
     run_planning_episodes,
 )
 from posggym_baselines_amd.planning.intmcp import INTMCP, BatchedINTMCP  # noqa: F401

@@ -501,6 +501,70 @@ class PomcpEngine:
             self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpBeliefCounts))), "episodes_belief_stats")
         return out
 
+    def episodes_set_population(self, probs=None, mixture_index=None):
+        """The other agents' population of the batches started from now on
+        (``pomcp_episodes_set_population``): ``probs`` = one action distribution
+        per policy (``get_pi`` in action order), ``mixture_index[k]`` = the index
+        of policy ``k``'s id among the planner's mixture policies or -1 (the
+        default for every policy); ``None``: back to the uniform random agent."""
+        if probs is None:
+            self._check(self._lib.pomcp_episodes_set_population(self._ctx, None),
+                        "episodes_set_population")
+            return
+        if not 1 <= len(probs) <= N.POMCP_MAX_TYPE_POLICIES:
+            raise ValueError(f"a population has 1 to {N.POMCP_MAX_TYPE_POLICIES} policies")
+        mix = [-1] * len(probs) if mixture_index is None else [int(j) for j in mixture_index]
+        if len(mix) != len(probs):
+            raise ValueError("one mixture_index per policy")
+        pop = N.PomcpEpisodePopulation()
+        pop.num_policies = len(probs)
+        for k, pi in enumerate(probs):
+            if len(pi) != self.A:
+                raise ValueError(f"policy {k}: {len(pi)} probabilities for {self.A} actions")
+            for a in range(self.A):
+                pop.pi[k][a] = float(pi[a])
+        for k in range(N.POMCP_MAX_TYPE_POLICIES):
+            pop.mixture_index[k] = mix[k] if k < len(mix) else -1
+        self._check(self._lib.pomcp_episodes_set_population(self._ctx, C.byref(pop)),
+                    "episodes_set_population")
+
+    def episodes_pop_states(self):
+        """Every tree's ``pomcp_episode_pop_state``: the policy index its episode
+        drew from the population (-1 without one) and that policy's mixture index."""
+        out = np.zeros(self.num_trees, dtype=N.EPISODE_POP_STATE_DTYPE)
+        self._check(self._lib.pomcp_episodes_pop_states(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodePopState))), "episodes_pop_states")
+        return out
+
+    def episodes_track_belief_acc(self, on, per_step=False):
+        """Accumulate the belief accuracies of every played step on the device
+        (``pomcp_episodes_track_belief_acc``), from the next ``episodes_begin``."""
+        self._check(self._lib.pomcp_episodes_track_belief_acc(
+            self._ctx, 1 if on else 0, 1 if on and per_step else 0), "episodes_track_belief_acc")
+
+    def episodes_belief_acc(self):
+        """Every tree's ``pomcp_episode_belief_acc``: the sequential FP64 sums of
+        its steps' state / policy / action accuracies, their count, its error."""
+        out = np.zeros(self.num_trees, dtype=N.EPISODE_BELIEF_ACC_DTYPE)
+        self._check(self._lib.pomcp_episodes_belief_acc(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeBeliefAcc))), "episodes_belief_acc")
+        return out
+
+    def episodes_belief_acc_steps(self, max_steps):
+        """The per-step table [num_trees][max_steps][3] (state, policy, action);
+        entries at t >= a tree's count are unspecified."""
+        out = np.zeros((self.num_trees, int(max_steps), 3), dtype=np.float64)
+        self._check(self._lib.pomcp_episodes_belief_acc_steps(
+            self._ctx, out.ctypes.data_as(C.POINTER(C.c_double))), "episodes_belief_acc_steps")
+        return out
+
+    def episodes_belief_acc_ms(self):
+        """Device milliseconds since ``episodes_begin`` spent in ``k_episode_belief_acc``."""
+        ms = C.c_double()
+        self._check(self._lib.pomcp_episodes_belief_acc_ms(self._ctx, C.byref(ms)),
+                    "episodes_belief_acc_ms")
+        return ms.value
+
     def episodes_timing(self):
         """Device milliseconds since ``episodes_begin`` spent in (updates,
         searches, the episode step kernels), and the number of steps."""

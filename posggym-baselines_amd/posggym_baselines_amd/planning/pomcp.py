@@ -403,10 +403,14 @@ class BatchedPOMCP:
     def __init__(self, model, agent_id, config: MCTSConfig, num_trees: int, num_sims: int,
                  *, searches: int = 1, reroot: bool = False, capacities=None, stream=None,
                  tree_key_base: int = 0, device: Optional[int] = None, type_policies=None,
-                 defer_cutoff: bool = True):
+                 defer_cutoff: bool = True, other_policy_ids=None):
         """defer_cutoff: defer cut-off children to the re-root (the default, the
         faster mode with or without an update after every search) or look them
-        up during the search (False); same results (``pomcp_set_defer_cutoff``)."""
+        up during the search (False); same results (``pomcp_set_defer_cutoff``).
+        other_policy_ids: the ids of ``type_policies``' other-agent policies in
+        their order (``list(OtherAgentMixturePolicy.policies)``); kept so that
+        ``run_episodes(other_agents=...)`` can tell which of a population's
+        policies the planners model."""
         from posggym_baselines_amd.planning.engine import plan_capacities
         if capacities is None:
             step_limit = config.step_limit or model.spec.max_episode_steps
@@ -417,6 +421,11 @@ class BatchedPOMCP:
             self._planned = None   # the caller's own capacities: not second-guessed
         self.num_trees = num_trees
         self.num_sims = num_sims
+        self.other_policy_ids = None if other_policy_ids is None else list(other_policy_ids)
+        if self.other_policy_ids is not None:
+            if type_policies is None or len(self.other_policy_ids) != type_policies.num_other:
+                raise ValueError("other_policy_ids names type_policies' other-agent policies, "
+                                 "one id each")
         self.engine = PomcpEngine(model, agent_id, config, num_trees=num_trees,
                                   capacities=capacities, stream=stream,
                                   tree_key_base=tree_key_base, device=device,
@@ -446,7 +455,8 @@ class BatchedPOMCP:
 
     # ------------------------------------------------------------ episodes
     def run_episodes(self, env_seeds=None, *, until: str = "agent_done",
-                     belief_states: bool = False, write_row=None, on_step=None):
+                     belief_states: bool = False, write_row=None, on_step=None,
+                     other_agents=None, belief_acc=False, track_per_step: bool = False):
         """Play one episode per tree against uniform random other agents, the
         whole batch in lockstep on the device; returns one result row per tree.
 
@@ -480,6 +490,26 @@ class BatchedPOMCP:
         ``on_step`` can track belief accuracy with no host copy of a state.
         ``write_row(row)`` is called per tree at the end; ``on_step(t, self)``
         after every step (tests: ``episode_states()`` is the debug getter).
+
+        ``other_agents``: a population for the other agent, an ordered list of 1
+        to 8 ``FixedDistributionPolicy`` with distinct ids; every tree draws its
+        episode's policy from it as ``PopulationAgents`` does for the serial
+        harness, on the device (``pomcp_episodes_set_population``), and the row
+        gains ``other_policy_id``.  A policy whose id is one of
+        ``other_policy_ids`` (the constructor's) is one the planners model.
+
+        ``belief_acc``: the row gains the ``BeliefStatTracker`` columns
+        (``get_stat_keys``: ``belief_{k}_acc``, with ``track_per_step`` also
+        ``belief_{k}_acc_{t}``, NaN past the episode's end), accumulated on the
+        device by ``k_episode_belief_acc`` after every step -- nothing per tree
+        comes to the host between steps.  ``True`` tracks ``policy``, ``action``,
+        ``state`` and ``history``; a list tracks the named ones (the tracker's
+        ``stats_to_track``).  Each mean is the tree's sequential FP64 sum of its
+        steps' values / their count (NaN for no step).  ``history`` is 0.0 with
+        ``state_belief_only`` and raises ``NotImplementedError`` otherwise, as
+        the tracker does; ``policy`` and ``action`` are 0.0 when the particles
+        carry no policy (``state_belief_only``), and ``policy`` is 0.0 for a
+        true policy the planners do not model (the uniform agent included).
         """
         from posggym_baselines_amd.planning.episodes import EPISODE_RESULT_HEADS
         if until not in ("agent_done", "all_done"):
@@ -499,9 +529,22 @@ class BatchedPOMCP:
                     f"run_episodes re-roots up to {max_steps} times per tree: create the engine "
                     f"with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one was "
                     f"sized with searches={searches}, reroot={reroot})")
+        acc_stats = self._belief_acc_stats(belief_acc)
+        if track_per_step and not acc_stats:
+            raise ValueError("track_per_step needs belief_acc")
+        pop_ids = pop_probs = mix = None
+        if other_agents is not None:
+            from posggym_baselines_amd.planning.episodes import check_population
+            other_agents = list(other_agents)
+            pop_probs = check_population(other_agents, self.engine.A)
+            pop_ids = [pol.policy_id for pol in other_agents]
+            known = self.other_policy_ids or []
+            mix = [known.index(i) if i in known else -1 for i in pop_ids]
         gamma = self.engine.config.discount
         pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
         start = time.time()
+        self.engine.episodes_set_population(pop_probs, mix)
+        self.engine.episodes_track_belief_acc(bool(acc_stats), track_per_step)
         self.engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states)
         live, t = B, 0
         while live > 0 and t < max_steps:
@@ -513,6 +556,30 @@ class BatchedPOMCP:
         (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
         elapsed = time.time() - start
         mem = psutil.Process().memory_info().rss / 1024**2
+        pops = self.engine.episodes_pop_states() if pop_ids is not None else None
+        acc = acc_steps = None
+        if acc_stats:
+            from posggym_baselines_amd.planning.utils import BeliefStatTracker
+            acc = self.engine.episodes_belief_acc()
+            if track_per_step:
+                acc_steps = self.engine.episodes_belief_acc_steps(max_steps)
+            # every column for all trees at once: (key, one value per tree), in the
+            # tracker's key order; sum / count is one IEEE division, as Python's
+            cnt = acc["count"].astype(np.int64)
+            played = cnt > 0
+            t_idx = np.arange(max_steps)[None, :] < cnt[:, None]
+            acc_columns = []
+            for key in BeliefStatTracker.get_stat_keys(acc_stats, track_per_step, max_steps):
+                k, _, t = key[len("belief_"):].partition("_acc")
+                if not t:       # the episode's mean
+                    v = 0.0 if k == "history" else acc[k + "_sum"] / np.maximum(cnt, 1)
+                    col = np.where(played, v, np.nan)
+                else:           # step t's value ("_<t>"), NaN past the episode's end
+                    t = int(t[1:])
+                    v = 0.0 if k == "history" else \
+                        acc_steps[:, t, ("state", "policy", "action").index(k)]
+                    col = np.where(t_idx[:, t], v, np.nan)
+                acc_columns.append((key, col.tolist()))
         rows = []
         for b in range(B):
             r = res[b]
@@ -530,10 +597,40 @@ class BatchedPOMCP:
                            num_sims=int(r["num_sims_sum"]) / n, mem_usage=mem,
                            min_value=float(r["min_value_sum"]) / n,
                            max_value=float(r["max_value_sum"]) / n)
+            if pops is not None:
+                row["other_policy_id"] = pop_ids[int(pops["policy_index"][b])]
+            if acc is not None:
+                for key, col in acc_columns:
+                    row[key] = col[b]
             if write_row is not None:
                 write_row(row)
             rows.append(row)
         return rows
+
+    def _belief_acc_stats(self, belief_acc):
+        """``run_episodes``' ``belief_acc`` as the tracker's ``stats_to_track``
+        ([] = off), refused as ``BeliefStatTracker`` refuses it."""
+        from posggym_baselines_amd.planning.utils import BeliefStatTracker
+        if belief_acc is None or belief_acc is False:
+            return []
+        if belief_acc is True:
+            stats = list(BeliefStatTracker.TRACKABLE_BELIEF_STATS)
+        else:
+            stats = list(belief_acc)
+            for k in stats:
+                if k not in BeliefStatTracker.TRACKABLE_BELIEF_STATS:
+                    raise ValueError(f"unknown belief stat {k!r}")
+        if "history" in stats and not self.engine.config.state_belief_only:
+            raise NotImplementedError(
+                "belief history accuracy: the GPU particles carry no joint history "
+                "(track it only with state_belief_only=True, where it is 0.0)")
+        return stats
+
+    def episode_belief_acc(self):
+        """Every tree's device belief accuracy record (``pomcp_episode_belief_acc``)
+        of ``run_episodes(..., belief_acc=...)``: the three sums, the count of
+        recorded steps, the error.  ``on_step`` may read it."""
+        return self.engine.episodes_belief_acc()
 
     def episode_states(self):
         """Every tree's device episode record (``pomcp_episode_state``) as a

@@ -18,9 +18,23 @@ run first), their ratio, and the device time of k_episode_step + the live count
 per step from events on the context stream (pomcp_episodes_timing).  The two
 routes' rows (length, return bits) must agree: exit status 1 if they do not.
 
+With ``--belief-acc`` it times the belief accuracy columns instead, on the same
+configuration: ``run_episodes(belief_acc=True)`` (k_episode_belief_acc after
+every step, nothing per tree on the host between steps) against the route it
+replaces, ``run_episodes(belief_states=True, on_step=...)`` whose callback
+fetches ``episode_belief_counts()`` (48 B per tree and step, every tree's belief
+reduced, parked ones too) and does the tracker's arithmetic in numpy.  Reported:
+wall time per step of both routes and of a run with no belief tracking, and the
+device time of k_episode_belief_acc per step (pomcp_episodes_belief_acc_ms).
+The two routes' ``belief_state_acc`` columns must agree bit for bit.  The record
+is stored under the key ``"belief_acc"`` of the ``--out`` file's record, beside
+the figures already there.
+
 Usage (one GPU process, under its own time limit):
 
     timeout -k 10 900 python tools/batched_episodes_timing.py \
+        --out profiles/batched_episodes_timing.json
+    timeout -k 10 900 python tools/batched_episodes_timing.py --belief-acc \
         --out profiles/batched_episodes_timing.json
 """
 import argparse
@@ -87,6 +101,60 @@ def host_route(bp, seeds, num_sims, max_steps):
     return [(int(lens[b]), float(rets[b]).hex()) for b in range(B)], steps, sec
 
 
+def belief_acc_timing(fresh, seeds, max_steps):
+    """(record, agree) of the --belief-acc comparison."""
+    import numpy as np
+
+    def timed(**kw):
+        bp = fresh()
+        try:
+            t0 = time.perf_counter()
+            rows = bp.run_episodes(seeds, until="all_done", **kw)
+            sec = time.perf_counter() - t0
+            _, steps = bp.engine.episodes_timing()
+            acc_ms = bp.engine.episodes_belief_acc_ms()
+        finally:
+            bp.close()
+        return rows, sec, steps, acc_ms
+
+    vals = []
+
+    def on_step(t, bp):
+        c = bp.episode_belief_counts()
+        n = c["belief_size"].astype(np.float64)
+        m = c["state_matches"].astype(np.float64)
+        vals.append(np.where(n > 0, m / np.maximum(n, 1.0), 0.0))
+
+    timed(belief_acc=True)                              # warm-up of both routes' kernels
+    timed(belief_states=True, on_step=on_step)
+    vals.clear()
+    plain_rows, plain_sec, plain_steps, _ = timed()
+    dev_rows, dev_sec, dev_steps, acc_ms = timed(belief_acc=True)
+    host_rows, host_sec, host_steps, _ = timed(belief_states=True, on_step=on_step)
+    t0 = time.perf_counter()
+    # the tracker's per-episode mean: a tree's steps are those before its length
+    lens = np.array([r["len"] for r in host_rows])
+    sums = np.zeros(len(seeds))
+    for t, v in enumerate(vals):
+        sums = sums + np.where(t < lens, v, 0.0)
+    host_acc = sums / lens
+    host_sec += time.perf_counter() - t0
+    agree = [float(r["belief_state_acc"]).hex() for r in dev_rows] == \
+        [float(x).hex() for x in host_acc]
+    agree = agree and [r["len"] for r in dev_rows] == [r["len"] for r in host_rows]
+    rec = {
+        "steps": dev_steps,
+        "plain_ms_per_step": plain_sec * 1e3 / plain_steps,
+        "belief_acc_ms_per_step": dev_sec * 1e3 / dev_steps,
+        "k_episode_belief_acc_ms_per_step": acc_ms / dev_steps,
+        "on_step_route_ms_per_step": host_sec * 1e3 / host_steps,
+        "on_step_route_over_belief_acc": (host_sec / host_steps) / (dev_sec / dev_steps),
+        "mean_belief_state_acc": float(np.mean(host_acc)),
+        "columns_agree": bool(agree),
+    }
+    return rec, agree
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--trees", type=int, default=4096)
@@ -94,6 +162,8 @@ def main():
     ap.add_argument("--first-seed", type=int, default=3000)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default="-", help="JSON record path ('-': stdout only)")
+    ap.add_argument("--belief-acc", action="store_true",
+                    help="time run_episodes(belief_acc=True) against the on_step route")
     args = ap.parse_args()
 
     import torch
@@ -112,6 +182,22 @@ def main():
         # must play the same episodes to be compared row by row
         return BatchedPOMCP(model, "0", MCTSConfig(seed=0, num_sims=S, **CFG), B, S,
                             searches=max_steps, reroot=True, device=dev)
+
+    if args.belief_acc:
+        acc_rec, agree = belief_acc_timing(fresh, seeds, max_steps)
+        acc_rec = dict({"trees": B, "sims": S, "device": torch.cuda.get_device_name(dev)},
+                       **acc_rec)
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["belief_acc"] = acc_rec
+        print(json.dumps(acc_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0 if agree else 1
 
     bp = fresh()
     try:
