@@ -1,21 +1,11 @@
 // C-ABI host side of the I-NTMCP engine (include/intmcp.h).  Part of the
 // single translation unit of pomcp_capi.hip.
-#include <type_traits>
-
 #include "../../include/intmcp.h"
+#include "host_ctx.h"
 
-struct intmcp_ctx {
+struct intmcp_ctx : HostCtx {
   intmcp_config cfg;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   ImParams ip{};
-  std::vector<void*> allocs;
-  std::string err;
-  DrvModel host_drv;
-  PeModel host_pe;
-  const void* host_model = nullptr;
-  size_t model_bytes = 0;
   std::vector<int32_t> host_out;
   std::vector<IHdr> host_hdr;
   intmcp_root_stats* dev_rstats = nullptr;   // device staging of intmcp_get_root_stats
@@ -67,43 +57,20 @@ __global__ __launch_bounds__(64) void k_im_root_stats(ImParams d, intmcp_root_st
   out[t] = o;
 }
 
-#define IM_TRY(ctx, expr)                                                           \
-  do {                                                                              \
-    hipError_t e_ = (expr);                                                         \
-    if (e_ != hipSuccess) {                                                         \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);              \
-      return POMCP_E_HIP;                                                           \
-    }                                                                               \
-  } while (0)
-
-#define IM_LAUNCH(ctx, KERNEL, grid, block, ...)                                              \
-  do {                                                                                         \
-    if ((ctx)->cfg.base.env_id == POMCP_ENV_PURSUIT_EVASION)                                   \
-      hipLaunchKernelGGL(KERNEL<EnvPursuitEvasion>, grid, block, 0, (ctx)->stream, __VA_ARGS__); \
-    else                                                                                       \
-      hipLaunchKernelGGL(KERNEL<EnvDriving>, grid, block, 0, (ctx)->stream, __VA_ARGS__);    \
-  } while (0)
-
 static unsigned im_blocks(int B) { return (unsigned)((B + 63) / 64); }
 
-static int im_alloc(intmcp_ctx* ctx, void** out, size_t bytes) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    ctx->err = "hipMalloc(" + std::to_string(bytes) + " B): " + hipGetErrorString(e);
-    return POMCP_E_HIP;
-  }
-  ctx->allocs.push_back(p);
-  *out = p;
-  return POMCP_OK;
+// f(Env{}) with the context's environment (envs.h)
+template <class F>
+static void im_with_env(const intmcp_ctx* ctx, F&& f) {
+  env_dispatch<EnvDriving, EnvPursuitEvasion>(ctx->cfg.base.env_id, f);
 }
 
-template <class T>
-static int im_copy(intmcp_ctx* ctx, T* dst, const T* src, size_t n) {
-  if (n == 0) return POMCP_OK;
-  IM_TRY(ctx, hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyDeviceToHost, ctx->stream));
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+// The first pair whose status code(t) is an error.
+template <class Code>
+static int im_first_error(intmcp_ctx* ctx, const char* what, Code code) {
+  return first_error(ctx, ctx->ip.B, code, [&](int t, int e) {
+    return std::string(what) + ": pair " + std::to_string(t) + ": status " + std::to_string(e);
+  });
 }
 
 // nodes 0..n-1 of one tree of one pair, packed as [n][kImBlock] (line, then
@@ -114,11 +81,11 @@ static int im_copy_blocks(intmcp_ctx* ctx, std::vector<char>& out, int pair, int
   if (n == 0) return POMCP_OK;
   const char* line0 = ctx->ip.nodes + im_node_off(ctx->ip.Nn, ctx->ip.B, pair, tree, 0, ctx->ip.nt);
   const size_t ns = (size_t)im_node_stride(ctx->ip.B, pair);
-  IM_TRY(ctx, hipMemcpy2DAsync(out.data(), kImBlock, line0, ns, kImLine, n, hipMemcpyDeviceToHost,
+  PB_TRY(ctx, hipMemcpy2DAsync(out.data(), kImBlock, line0, ns, kImLine, n, hipMemcpyDeviceToHost,
                                ctx->stream));
-  IM_TRY(ctx, hipMemcpy2DAsync(out.data() + kImLine, kImBlock, line0 + im_rec_delta(ctx->ip.B, pair),
+  PB_TRY(ctx, hipMemcpy2DAsync(out.data() + kImLine, kImBlock, line0 + im_rec_delta(ctx->ip.B, pair),
                                ns, kImRecs, n, hipMemcpyDeviceToHost, ctx->stream));
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return POMCP_OK;
 }
 
@@ -130,10 +97,7 @@ const char* intmcp_last_error(const intmcp_ctx* ctx) { return ctx ? ctx->err.c_s
 
 void intmcp_destroy(intmcp_ctx* ctx) {
   if (!ctx) return;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (void* p : ctx->allocs) (void)hipFree(p);
-  if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  ctx->close();
   delete ctx;
 }
 
@@ -141,14 +105,10 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
   if (!cfg || !out) return POMCP_E_INVALID;
   *out = nullptr;
   const pomcp_config& c = cfg->base;
-  auto* ctx = new intmcp_ctx();
-  ctx->cfg = *cfg;
   g_create_err.clear();
   auto bad = [&](int code, const char* m) {
     g_create_err = m;
-    int rc = code;
-    delete ctx;
-    return rc;
+    return code;
   };
   if (c.abi_version != POMCP_ABI_VERSION) return bad(POMCP_E_INVALID, "ABI version mismatch");
   if (c.env_id != POMCP_ENV_DRIVING && c.env_id != POMCP_ENV_PURSUIT_EVASION)
@@ -168,35 +128,14 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
     return bad(POMCP_E_INVALID, "capacities");
   if (!c.log_table || c.log_table_size < 2 || !c.discount_pow || c.discount_pow_size < 1)
     return bad(POMCP_E_INVALID, "tables");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0) {
+  auto* ctx = new intmcp_ctx();
+  ctx->cfg = *cfg;
+  int rc = ctx->open(device, hip_stream);
+  if (rc != POMCP_OK) {
     delete ctx;
-    return POMCP_E_NO_DEVICE;
+    return rc;
   }
-  ctx->device = device;
-  if (hipSetDevice(device) != hipSuccess) {
-    delete ctx;
-    return POMCP_E_NO_DEVICE;
-  }
-  if (hip_stream) {
-    ctx->stream = (hipStream_t)hip_stream;
-  } else {
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete ctx;
-      return POMCP_E_HIP;
-    }
-    ctx->own_stream = true;
-  }
-  if (c.env_id == POMCP_ENV_PURSUIT_EVASION) {
-    build_pe_model(c.pe_grid, &ctx->host_pe);
-    ctx->host_model = &ctx->host_pe;
-    ctx->model_bytes = sizeof(PeModel);
-  } else {
-    std::memcpy(&ctx->host_drv.g, &c.grid, sizeof(DrvGrid));
-    build_model_tables(ctx->host_drv.g, &ctx->host_drv);
-    ctx->host_model = &ctx->host_drv;
-    ctx->model_bytes = sizeof(DrvModel);
-  }
+  ctx->set_env_model(c);
   ImParams& d = ctx->ip;
   d.fast_slack = IM_FAST_SLACK;
   d.B = c.num_trees;
@@ -225,41 +164,38 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
   d.Nr = cfg->max_root_belief;
   d.Nsp = cfg->max_support_particles;
   const int64_t B = c.num_trees;
-  int rc;
-  void* p;
-#define IM_ALLOC(field, type, count)                                            \
-  do {                                                                          \
-    if ((rc = im_alloc(ctx, &p, sizeof(type) * (size_t)(count))) != POMCP_OK) {\
-      g_create_err = ctx->err;                                                  \
-      intmcp_destroy(ctx);                                                      \
-      return rc;                                                                \
-    }                                                                           \
-    d.field = reinterpret_cast<std::remove_reference_t<decltype(d.field)>>(p);  \
-  } while (0)
-  IM_ALLOC(hdr, IHdr, B);
+  // (the first failure skips the rest)
+  auto alloc = [&](auto*& field, int64_t count) {
+    if (rc == POMCP_OK) rc = ctx->alloc(field, (size_t)count);
+  };
+  alloc(d.hdr, B);
   d.nstride = kImBlock;   // node blocks (intmcp.hip), interleaved by wave: im_node_off
-  IM_ALLOC(nodes, char, B * d.nt * d.Nn * d.nstride);
-  IM_ALLOC(hash, IHash, B * d.nt * d.H);
-  IM_ALLOC(log, IRec, B * d.nt * d.Nl);
-  IM_ALLOC(root, uint4, B * 2 * d.Nr);
-  IM_ALLOC(sup, ISup, B * 2 * d.Nr);
-  IM_ALLOC(supp, uint2, B * 2 * d.Nsp);
+  alloc(d.nodes, B * d.nt * d.Nn * d.nstride);
+  alloc(d.hash, B * d.nt * d.H);
+  alloc(d.log, B * d.nt * d.Nl);
+  alloc(d.root, B * 2 * d.Nr);
+  alloc(d.sup, B * 2 * d.Nr);
+  alloc(d.supp, B * 2 * d.Nsp);
   for (int m = 0; m < kImMaxMid; ++m) {   // the middle planners' beliefs and distributions
     const bool mid = m < d.nt - 2;
-    IM_ALLOC(msup[m], ISup, mid ? B * 2 * d.Nr : 1);
-    IM_ALLOC(msupp[m], uint4, mid ? B * 2 * d.Nsp : 1);
-    IM_ALLOC(mprob[m], double, mid ? B * d.Nr : 1);
+    alloc(d.msup[m], mid ? B * 2 * d.Nr : 1);
+    alloc(d.msupp[m], mid ? B * 2 * d.Nsp : 1);
+    alloc(d.mprob[m], mid ? B * d.Nr : 1);
   }
-  IM_ALLOC(path, int4, B * kImPath * 3);
-  IM_ALLOC(prob, double, B * d.Nr);
-  IM_ALLOC(logtab, double, c.log_table_size);
-  IM_ALLOC(dpow, double, c.discount_pow_size);
-  IM_ALLOC(model, uint8_t, ctx->model_bytes);
-  IM_ALLOC(in_actions, int32_t, B);
-  IM_ALLOC(in_obs, uint64_t, B);
-  IM_ALLOC(out, int32_t, B * 2);
-  IM_ALLOC(out_obs, uint64_t, B);
-#undef IM_ALLOC
+  alloc(d.path, B * kImPath * 3);
+  alloc(d.prob, B * d.Nr);
+  alloc(d.logtab, c.log_table_size);
+  alloc(d.dpow, c.discount_pow_size);
+  if (rc == POMCP_OK) rc = ctx->alloc_bytes(d.model, ctx->model_bytes);
+  alloc(d.in_actions, B);
+  alloc(d.in_obs, B);
+  alloc(d.out, B * 2);
+  alloc(d.out_obs, B);
+  if (rc != POMCP_OK) {
+    g_create_err = ctx->err;
+    intmcp_destroy(ctx);
+    return rc;
+  }
   d.logtab_n = c.log_table_size;
   d.dpow_n = (int32_t)(c.discount_pow_size > INT32_MAX ? INT32_MAX : c.discount_pow_size);
   std::vector<IHdr> h((size_t)B);
@@ -268,16 +204,11 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
     h[t].seed = c.seed;
     h[t].tree_key = c.tree_key_base + (uint32_t)t;
   }
-  hipStream_t s = ctx->stream;
-  if (hipMemcpyAsync((void*)d.logtab, c.log_table, sizeof(double) * c.log_table_size,
-                     hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync((void*)d.dpow, c.discount_pow, sizeof(double) * c.discount_pow_size,
-                     hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync((void*)d.model, ctx->host_model, ctx->model_bytes, hipMemcpyHostToDevice,
-                     s) != hipSuccess ||
-      hipMemcpyAsync(d.hdr, h.data(), sizeof(IHdr) * (size_t)B, hipMemcpyHostToDevice, s) !=
-          hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
+  if (ctx->upload(d.logtab, c.log_table, (size_t)c.log_table_size) != POMCP_OK ||
+      ctx->upload(d.dpow, c.discount_pow, (size_t)c.discount_pow_size) != POMCP_OK ||
+      ctx->upload_bytes(d.model, ctx->host_model, ctx->model_bytes) != POMCP_OK ||
+      ctx->upload(d.hdr, h.data(), (size_t)B) != POMCP_OK ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess) {
     g_create_err = "initial upload failed";
     intmcp_destroy(ctx);
     return POMCP_E_HIP;
@@ -296,85 +227,70 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
 
 int intmcp_reset(intmcp_ctx* ctx) {
   if (!ctx) return POMCP_E_INVALID;
-  IM_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   // node lines and records start zeroed: statistics and inline child slots
   // need no initialising writes (intmcp.hip, kImBlock)
-  IM_TRY(ctx, hipMemsetAsync(ctx->ip.nodes, 0, (size_t)ctx->ip.B * ctx->ip.nt * ctx->ip.Nn * kImBlock,
+  PB_TRY(ctx, hipMemsetAsync(ctx->ip.nodes, 0, (size_t)ctx->ip.B * ctx->ip.nt * ctx->ip.Nn * kImBlock,
                              ctx->stream));
   const int64_t slots = (int64_t)ctx->ip.B * ctx->ip.nt * ctx->ip.H;
   const int64_t cblocks = std::min<int64_t>((slots + 255) / 256, 256 * 64);
   hipLaunchKernelGGL(k_im_clear_hash, dim3((unsigned)cblocks), dim3(256), 0, ctx->stream, ctx->ip.hash,
                      slots);
-  IM_LAUNCH(ctx, k_im_reset, dim3(im_blocks(ctx->ip.B)), dim3(64), ctx->ip);
-  IM_TRY(ctx, hipGetLastError());
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
-}
-
-static int im_first_error(intmcp_ctx* ctx, const char* what) {
-  for (int t = 0; t < ctx->ip.B; ++t) {
-    const int e = ctx->host_out[2 * t + 1];
-    if (e != 0) {
-      ctx->err = std::string(what) + ": pair " + std::to_string(t) + ": status " + std::to_string(e);
-      return e;
-    }
-  }
+  im_with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_im_reset<decltype(e)>, dim3(im_blocks(ctx->ip.B)), dim3(64), 0, ctx->stream,
+                       ctx->ip);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return POMCP_OK;
 }
 
 int intmcp_update(intmcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_keys,
                   int32_t* root_absorbing_out) {
   if (!ctx || !obs_keys) return POMCP_E_INVALID;
-  IM_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->ip.B;
   std::vector<int32_t> acts((size_t)B, -1);
   if (actions) std::memcpy(acts.data(), actions, sizeof(int32_t) * (size_t)B);
-  IM_TRY(ctx, hipMemcpyAsync((void*)ctx->ip.in_actions, acts.data(), sizeof(int32_t) * B,
-                             hipMemcpyHostToDevice, ctx->stream));
-  IM_TRY(ctx, hipMemcpyAsync((void*)ctx->ip.in_obs, obs_keys, sizeof(uint64_t) * B,
-                             hipMemcpyHostToDevice, ctx->stream));
+  int rc;
+  if ((rc = ctx->upload(ctx->ip.in_actions, acts.data(), (size_t)B)) != POMCP_OK ||
+      (rc = ctx->upload(ctx->ip.in_obs, obs_keys, (size_t)B)) != POMCP_OK)
+    return rc;
   // a wave per pair for few pairs (the drop-in): the update's log scans are
   // shared by the wave's lanes (k_im_update kWave); a lane per pair otherwise
   const bool wave = B <= 1024;
   const dim3 ugrid(wave ? (unsigned)B : (unsigned)im_blocks(B));
-#define IM_UPDATE_N(NT)                                                                                     \
-  do {                                                                                                      \
-    if (ctx->cfg.base.env_id == POMCP_ENV_PURSUIT_EVASION) {                                                \
-      if (wave) hipLaunchKernelGGL((k_im_updateN<EnvPursuitEvasion, NT, true>), ugrid, dim3(64), 0, ctx->stream, ctx->ip); \
-      else hipLaunchKernelGGL((k_im_updateN<EnvPursuitEvasion, NT, false>), ugrid, dim3(64), 0, ctx->stream, ctx->ip); \
-    } else {                                                                                                \
-      if (wave) hipLaunchKernelGGL((k_im_updateN<EnvDriving, NT, true>), ugrid, dim3(64), 0, ctx->stream, ctx->ip); \
-      else hipLaunchKernelGGL((k_im_updateN<EnvDriving, NT, false>), ugrid, dim3(64), 0, ctx->stream, ctx->ip); \
-    }                                                                                                       \
-  } while (0)
-  if (ctx->ip.nt == 6) {   // nesting level 5
-    IM_UPDATE_N(6);
-  } else if (ctx->ip.nt == 5) {   // nesting level 4
-    IM_UPDATE_N(5);
-  } else if (ctx->ip.nt == 4) {   // nesting level 3
-    IM_UPDATE_N(4);
-  } else if (ctx->ip.nt == 3) {   // nesting level 2
-    IM_UPDATE_N(3);
-  } else if (ctx->cfg.base.env_id == POMCP_ENV_PURSUIT_EVASION) {
-    if (wave) hipLaunchKernelGGL((k_im_update<EnvPursuitEvasion, true>), ugrid, dim3(64), 0, ctx->stream, ctx->ip);
-    else hipLaunchKernelGGL((k_im_update<EnvPursuitEvasion, false>), ugrid, dim3(64), 0, ctx->stream, ctx->ip);
-  } else {
-    if (wave) hipLaunchKernelGGL((k_im_update<EnvDriving, true>), ugrid, dim3(64), 0, ctx->stream, ctx->ip);
-    else hipLaunchKernelGGL((k_im_update<EnvDriving, false>), ugrid, dim3(64), 0, ctx->stream, ctx->ip);
-  }
-  IM_TRY(ctx, hipGetLastError());
-  IM_TRY(ctx, hipMemcpyAsync(ctx->host_out.data(), ctx->ip.out, sizeof(int32_t) * 2 * B,
-                             hipMemcpyDeviceToHost, ctx->stream));
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  im_with_env(ctx, [&](auto e) {
+    dispatch<std::false_type, std::true_type>(wave, [&](auto w) {
+      using E = decltype(e);
+      constexpr bool W = decltype(w)::value;
+      if (ctx->ip.nt == 2)   // nesting levels 0 and 1
+        hipLaunchKernelGGL((k_im_update<E, W>), ugrid, dim3(64), 0, ctx->stream, ctx->ip);
+      else   // a tree per nesting level from level 2
+        dispatch<Int<3>, Int<4>, Int<5>, Int<6>>(ctx->ip.nt - 3, [&](auto nt) {
+          hipLaunchKernelGGL((k_im_updateN<E, decltype(nt)::value, W>), ugrid, dim3(64), 0, ctx->stream,
+                             ctx->ip);
+        });
+    });
+  });
+  PB_TRY(ctx, hipGetLastError());
+  if ((rc = ctx->fetch(ctx->host_out.data(), ctx->ip.out, 2 * (size_t)B)) != POMCP_OK) return rc;
   if (root_absorbing_out)
     for (int t = 0; t < B; ++t) root_absorbing_out[t] = ctx->host_out[2 * t];
-  return im_first_error(ctx, "update");
+  return im_first_error(ctx, "update", [&](int t) { return ctx->host_out[2 * (size_t)t + 1]; });
 }
 
 static int im_fetch_hdr(intmcp_ctx* ctx) {
-  IM_TRY(ctx, hipMemcpyAsync(ctx->host_hdr.data(), ctx->ip.hdr, sizeof(IHdr) * ctx->ip.B,
-                             hipMemcpyDeviceToHost, ctx->stream));
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return ctx->fetch(ctx->host_hdr.data(), ctx->ip.hdr, (size_t)ctx->ip.B);
+}
+
+// The actions of a finished search from the pairs' headers, or its first error.
+static int im_search_actions(intmcp_ctx* ctx, int32_t* actions_out) {
+  int rc = im_fetch_hdr(ctx);
+  if (rc != POMCP_OK) return rc;
+  rc = im_first_error(ctx, "search", [&](int t) { return ctx->host_hdr[t].err; });
+  if (rc != POMCP_OK) return rc;
+  for (int t = 0; t < ctx->ip.B; ++t) actions_out[t] = ctx->host_hdr[t].last_action;
   return POMCP_OK;
 }
 
@@ -385,63 +301,36 @@ int intmcp_search_levels(intmcp_ctx* ctx, int32_t level0_sims, int32_t level1_si
                          int32_t flags, int32_t* actions_out) {
   if (!ctx || level0_sims < 0 || level1_sims < 0 || (flags & ~(kImBegin | kImFinal)))
     return POMCP_E_INVALID;
-  if (ctx->ip.nest0 && level1_sims > 0) {
-    ctx->err = "search_levels: nesting level 0 has no level-1 simulations";
-    return POMCP_E_INVALID;
-  }
+  if (ctx->ip.nest0 && level1_sims > 0)
+    return fail(ctx, POMCP_E_INVALID, "search_levels: nesting level 0 has no level-1 simulations");
   if (ctx->ip.nt >= 3) {
     int32_t sims[kImMaxT] = {};
     sims[0] = level0_sims;
     sims[1] = level1_sims;
     return im_searchN(ctx, sims, flags, actions_out);
   }
-  IM_TRY(ctx, hipSetDevice(ctx->device));
-  IM_LAUNCH(ctx, k_im_search, dim3(im_blocks(ctx->ip.B)), dim3(64), ctx->ip, (int)level0_sims,
-            (int)level1_sims, (int)flags);
-  IM_TRY(ctx, hipGetLastError());
-  if (!actions_out) return POMCP_OK;
-  int rc = im_fetch_hdr(ctx);
-  if (rc != POMCP_OK) return rc;
-  for (int t = 0; t < ctx->ip.B; ++t) {
-    if (ctx->host_hdr[t].err != 0) {
-      ctx->err = "search: pair " + std::to_string(t) + ": status " + std::to_string(ctx->host_hdr[t].err);
-      return ctx->host_hdr[t].err;
-    }
-    actions_out[t] = ctx->host_hdr[t].last_action;
-  }
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  im_with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_im_search<decltype(e)>, dim3(im_blocks(ctx->ip.B)), dim3(64), 0, ctx->stream,
+                       ctx->ip, (int)level0_sims, (int)level1_sims, (int)flags);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  return actions_out ? im_search_actions(ctx, actions_out) : POMCP_OK;
 }
 
 static int im_searchN(intmcp_ctx* ctx, const int32_t sims[kImMaxT], int32_t flags, int32_t* actions_out) {
-  IM_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const dim3 grid(im_blocks(ctx->ip.B));
-  const bool pe = ctx->cfg.base.env_id == POMCP_ENV_PURSUIT_EVASION;
   ImSims s{};
   for (int l = 0; l < ctx->ip.nt; ++l) s.s[l] = sims[l];
-#define IM_SEARCH_N(NT)                                                                                      \
-  do {                                                                                                       \
-    if (pe) hipLaunchKernelGGL((k_im_searchN<EnvPursuitEvasion, NT>), grid, dim3(64), 0, ctx->stream, ctx->ip, s, (int)flags); \
-    else hipLaunchKernelGGL((k_im_searchN<EnvDriving, NT>), grid, dim3(64), 0, ctx->stream, ctx->ip, s, (int)flags); \
-  } while (0)
-  switch (ctx->ip.nt) {   // a tree per nesting level
-    case 6: IM_SEARCH_N(6); break;
-    case 5: IM_SEARCH_N(5); break;
-    case 4: IM_SEARCH_N(4); break;
-    default: IM_SEARCH_N(3); break;
-  }
-#undef IM_SEARCH_N
-  IM_TRY(ctx, hipGetLastError());
-  if (!actions_out) return POMCP_OK;
-  int rc = im_fetch_hdr(ctx);
-  if (rc != POMCP_OK) return rc;
-  for (int t = 0; t < ctx->ip.B; ++t) {
-    if (ctx->host_hdr[t].err != 0) {
-      ctx->err = "search: pair " + std::to_string(t) + ": status " + std::to_string(ctx->host_hdr[t].err);
-      return ctx->host_hdr[t].err;
-    }
-    actions_out[t] = ctx->host_hdr[t].last_action;
-  }
-  return POMCP_OK;
+  im_with_env(ctx, [&](auto e) {   // a tree per nesting level
+    dispatch<Int<3>, Int<4>, Int<5>, Int<6>>(ctx->ip.nt - 3, [&](auto nt) {
+      hipLaunchKernelGGL((k_im_searchN<decltype(e), decltype(nt)::value>), grid, dim3(64), 0, ctx->stream,
+                         ctx->ip, s, (int)flags);
+    });
+  });
+  PB_TRY(ctx, hipGetLastError());
+  return actions_out ? im_search_actions(ctx, actions_out) : POMCP_OK;
 }
 
 int intmcp_search(intmcp_ctx* ctx, int32_t num_sims, int32_t* actions_out) {
@@ -459,10 +348,8 @@ int intmcp_search_level(intmcp_ctx* ctx, int32_t level, int32_t sims, int32_t fl
                         int32_t* actions_out) {
   if (!ctx || sims < 0 || (flags & ~(kImBegin | kImFinal))) return POMCP_E_INVALID;
   const int top = ctx->ip.nest0 ? 0 : ctx->ip.nt - 1;   // the planner's nesting level
-  if (level < 0 || level > top) {
-    ctx->err = "search_level: no level " + std::to_string(level);
-    return POMCP_E_INVALID;
-  }
+  if (level < 0 || level > top)
+    return fail(ctx, POMCP_E_INVALID, "search_level: no level " + std::to_string(level));
   if (ctx->ip.nt >= 3) {
     int32_t s[kImMaxT] = {};
     s[level] = sims;
@@ -473,29 +360,18 @@ int intmcp_search_level(intmcp_ctx* ctx, int32_t level, int32_t sims, int32_t fl
 
 int intmcp_get_root_stats(intmcp_ctx* ctx, intmcp_root_stats* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  IM_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->ip.B;
-  if (!ctx->dev_rstats) {
-    void* p = nullptr;
-    const int rc = im_alloc(ctx, &p, sizeof(intmcp_root_stats) * (size_t)B);
-    if (rc != POMCP_OK) return rc;
-    ctx->dev_rstats = reinterpret_cast<intmcp_root_stats*>(p);
-  }
+  int rc;
+  if (!ctx->dev_rstats && (rc = ctx->alloc(ctx->dev_rstats, (size_t)B)) != POMCP_OK) return rc;
   // one lane per pair gathers its root's record, then a single copy
   hipLaunchKernelGGL(k_im_root_stats, dim3(im_blocks(B)), dim3(64), 0, ctx->stream, ctx->ip,
                      ctx->dev_rstats);
-  IM_TRY(ctx, hipGetLastError());
-  const int rc = im_copy(ctx, out, ctx->dev_rstats, (size_t)B);
-  if (rc != POMCP_OK) return rc;
+  PB_TRY(ctx, hipGetLastError());
+  if ((rc = ctx->fetch(out, ctx->dev_rstats, (size_t)B)) != POMCP_OK) return rc;
   // a failed search (arena, depleted root, ...) is reported here, as
   // pomcp_get_root_stats does: its partial tree's action must not be used
-  for (int t = 0; t < B; ++t) {
-    if (out[t].error != 0) {
-      ctx->err = "search: pair " + std::to_string(t) + ": status " + std::to_string(out[t].error);
-      return out[t].error;
-    }
-  }
-  return POMCP_OK;
+  return im_first_error(ctx, "search", [&](int t) { return out[t].error; });
 }
 
 int intmcp_get_root_belief(intmcp_ctx* ctx, int32_t pair, uint32_t* out, int32_t capacity,
@@ -507,7 +383,7 @@ int intmcp_get_root_belief(intmcp_ctx* ctx, int32_t pair, uint32_t* out, int32_t
   *count = h.root_size;
   if (!out || capacity < h.root_size) return POMCP_OK;
   std::vector<uint4> buf((size_t)h.root_size);
-  rc = im_copy(ctx, buf.data(), ctx->ip.root + ((int64_t)pair * 2 + h.root_sel) * ctx->ip.Nr,
+  rc = ctx->fetch(buf.data(), ctx->ip.root + ((int64_t)pair * 2 + h.root_sel) * ctx->ip.Nr,
                (size_t)h.root_size);
   if (rc != POMCP_OK) return rc;
   for (int i = 0; i < h.root_size; ++i) {
@@ -598,17 +474,15 @@ int intmcp_debug_phase_timing(intmcp_ctx* ctx, uint64_t* out, int32_t capacity, 
 #else
   const size_t n = (size_t)kImPhases * (size_t)ctx->ip.B;
   if (ctx->ip.timing == nullptr) {
-    void* p = nullptr;
-    if (im_alloc(ctx, &p, sizeof(uint64_t) * n) != POMCP_OK) return POMCP_E_HIP;
-    IM_TRY(ctx, hipMemset(p, 0, sizeof(uint64_t) * n));
-    ctx->ip.timing = reinterpret_cast<uint64_t*>(p);
+    if (ctx->alloc(ctx->ip.timing, n) != POMCP_OK) return POMCP_E_HIP;
+    PB_TRY(ctx, hipMemset(ctx->ip.timing, 0, sizeof(uint64_t) * n));
     *count = 0;
     return POMCP_OK;
   }
   *count = (int32_t)n;
   if (out && capacity >= *count) {
-    IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    IM_TRY(ctx, hipMemcpy(out, ctx->ip.timing, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+    PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    PB_TRY(ctx, hipMemcpy(out, ctx->ip.timing, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
   }
   return POMCP_OK;
 #endif
@@ -621,10 +495,8 @@ int intmcp_debug_phase_timing(intmcp_ctx* ctx, uint64_t* out, int32_t capacity, 
 int intmcp_debug_set_softmax_slack(intmcp_ctx* ctx, float slack) {
   if (!ctx || !(slack >= 1.0f)) return POMCP_E_INVALID;
   if (ctx->ip.exact_draws == nullptr) {
-    void* p = nullptr;
-    if (im_alloc(ctx, &p, sizeof(unsigned long long)) != POMCP_OK) return POMCP_E_HIP;
-    IM_TRY(ctx, hipMemsetAsync(p, 0, sizeof(unsigned long long), ctx->stream));
-    ctx->ip.exact_draws = reinterpret_cast<unsigned long long*>(p);
+    if (ctx->alloc(ctx->ip.exact_draws, 1) != POMCP_OK) return POMCP_E_HIP;
+    PB_TRY(ctx, hipMemsetAsync(ctx->ip.exact_draws, 0, sizeof(unsigned long long), ctx->stream));
   }
   ctx->ip.fast_slack = slack;
   return POMCP_OK;
@@ -633,10 +505,8 @@ int intmcp_debug_set_softmax_slack(intmcp_ctx* ctx, float slack) {
 int intmcp_set_search_policy(intmcp_ctx* ctx, int32_t level, int32_t agent, const double* probs) {
   if (!ctx || agent < 0 || agent > 1) return POMCP_E_INVALID;
   const int top = ctx->ip.nest0 ? 0 : ctx->ip.nt - 1;   // the planner's nesting level
-  if (level < 0 || level > top) {
-    ctx->err = "set_search_policy: no planner at level " + std::to_string(level);
-    return POMCP_E_INVALID;
-  }
+  if (level < 0 || level > top)
+    return fail(ctx, POMCP_E_INVALID, "set_search_policy: no planner at level " + std::to_string(level));
   const int k = top - level;               // tree 0 = the top level; the level-0 planner's is the last
   const int tree = ctx->ip.nest0 ? 1 : k;
   ImParams& d = ctx->ip;
@@ -647,17 +517,12 @@ int intmcp_set_search_policy(intmcp_ctx* ctx, int32_t level, int32_t agent, cons
     // itertools.accumulate does, and total = cum[-1] + 0.0
     double acc = 0.0;
     for (int a = 0; a < d.A; ++a) {
-      if (!(probs[a] >= 0.0)) {
-        ctx->err = "set_search_policy: negative or NaN weight";
-        return POMCP_E_INVALID;
-      }
+      if (!(probs[a] >= 0.0))
+        return fail(ctx, POMCP_E_INVALID, "set_search_policy: negative or NaN weight");
       acc = a == 0 ? probs[0] : acc + probs[a];
       d.sp_cum[tree][agent][a] = acc;
     }
-    if (!(acc > 0.0)) {
-      ctx->err = "set_search_policy: weights sum to zero";
-      return POMCP_E_INVALID;
-    }
+    if (!(acc > 0.0)) return fail(ctx, POMCP_E_INVALID, "set_search_policy: weights sum to zero");
     d.sp_tot[tree][agent] = acc + 0.0;
     d.sp_fixed[tree][agent] = 1;
   }
@@ -671,10 +536,8 @@ int intmcp_debug_exact_draws(intmcp_ctx* ctx, uint64_t* count) {
   if (!ctx || !count) return POMCP_E_INVALID;
   *count = 0;
   if (ctx->ip.exact_draws == nullptr) return POMCP_OK;
-  IM_TRY(ctx, hipMemcpyAsync(count, ctx->ip.exact_draws, sizeof(uint64_t), hipMemcpyDeviceToHost,
-                             ctx->stream));
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "exact-draw counter");
+  return ctx->fetch(reinterpret_cast<unsigned long long*>(count), ctx->ip.exact_draws, 1);
 }
 
 int intmcp_get_support(intmcp_ctx* ctx, int32_t pair, int32_t* entries, int32_t capacity_entries,
@@ -687,12 +550,12 @@ int intmcp_get_support(intmcp_ctx* ctx, int32_t pair, int32_t* entries, int32_t 
   *n_entries = h.n_sup;
   *n_particles = h.sup_used;
   if (entries && capacity_entries >= h.n_sup) {
-    rc = im_copy(ctx, reinterpret_cast<ISup*>(entries),
+    rc = ctx->fetch(reinterpret_cast<ISup*>(entries),
                  ctx->ip.sup + ((int64_t)pair * 2 + h.sup_sel) * ctx->ip.Nr, (size_t)h.n_sup);
     if (rc != POMCP_OK) return rc;
   }
   if (particles && capacity_particles >= h.sup_used) {
-    rc = im_copy(ctx, reinterpret_cast<uint2*>(particles),
+    rc = ctx->fetch(reinterpret_cast<uint2*>(particles),
                  ctx->ip.supp + ((int64_t)pair * 2 + h.sup_sel) * ctx->ip.Nsp, (size_t)h.sup_used);
     if (rc != POMCP_OK) return rc;
   }
@@ -703,10 +566,9 @@ int intmcp_get_middle_support(intmcp_ctx* ctx, int32_t pair, int32_t tree, int32
                               int32_t capacity_entries, int32_t* n_entries, uint32_t* particles,
                               int32_t capacity_particles, int32_t* n_particles) {
   if (!ctx || !n_entries || !n_particles || pair < 0 || pair >= ctx->ip.B) return POMCP_E_INVALID;
-  if (tree < 1 || tree > ctx->ip.nt - 2) {
-    ctx->err = "get_middle_support: no middle tree " + std::to_string(tree) + " (nesting levels >= 2)";
-    return POMCP_E_INVALID;
-  }
+  if (tree < 1 || tree > ctx->ip.nt - 2)
+    return fail(ctx, POMCP_E_INVALID,
+                "get_middle_support: no middle tree " + std::to_string(tree) + " (nesting levels >= 2)");
   int rc = im_fetch_hdr(ctx);
   if (rc != POMCP_OK) return rc;
   const IHdr& h = ctx->host_hdr[pair];
@@ -714,13 +576,13 @@ int intmcp_get_middle_support(intmcp_ctx* ctx, int32_t pair, int32_t tree, int32
   *n_entries = h.n_msup[m];
   *n_particles = h.msup_used[m];
   if (entries && capacity_entries >= h.n_msup[m]) {
-    rc = im_copy(ctx, reinterpret_cast<ISup*>(entries),
+    rc = ctx->fetch(reinterpret_cast<ISup*>(entries),
                  ctx->ip.msup[m] + ((int64_t)pair * 2 + h.msel[m]) * ctx->ip.Nr, (size_t)h.n_msup[m]);
     if (rc != POMCP_OK) return rc;
   }
   if (particles && capacity_particles >= h.msup_used[m]) {
     std::vector<uint4> buf((size_t)h.msup_used[m]);
-    rc = im_copy(ctx, buf.data(), ctx->ip.msupp[m] + ((int64_t)pair * 2 + h.msel[m]) * ctx->ip.Nsp,
+    rc = ctx->fetch(buf.data(), ctx->ip.msupp[m] + ((int64_t)pair * 2 + h.msel[m]) * ctx->ip.Nsp,
                  (size_t)h.msup_used[m]);
     if (rc != POMCP_OK) return rc;
     for (int i = 0; i < h.msup_used[m]; ++i) {
@@ -757,14 +619,14 @@ int intmcp_get_tree_counts(intmcp_ctx* ctx, int32_t* out) {
 
 int intmcp_synthetic_obs(intmcp_ctx* ctx, uint64_t env_seed_base, uint64_t* obs_keys_out) {
   if (!ctx) return POMCP_E_INVALID;
-  IM_TRY(ctx, hipSetDevice(ctx->device));
-  IM_LAUNCH(ctx, k_im_synthetic, dim3(im_blocks(ctx->ip.B)), dim3(64), ctx->ip, env_seed_base);
-  IM_TRY(ctx, hipGetLastError());
-  if (obs_keys_out) {
-    IM_TRY(ctx, hipMemcpyAsync(obs_keys_out, ctx->ip.out_obs, sizeof(uint64_t) * ctx->ip.B,
-                               hipMemcpyDeviceToHost, ctx->stream));
-  }
-  IM_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  im_with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_im_synthetic<decltype(e)>, dim3(im_blocks(ctx->ip.B)), dim3(64), 0, ctx->stream,
+                       ctx->ip, env_seed_base);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  if (obs_keys_out) return ctx->fetch(obs_keys_out, ctx->ip.out_obs, (size_t)ctx->ip.B);
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return POMCP_OK;
 }
 

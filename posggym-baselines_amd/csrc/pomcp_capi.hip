@@ -27,6 +27,7 @@
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
 #include "intmcp.hip"
 #include "../../include/pomcp_debug.h"
+#include "host_ctx.h"
 
 using namespace pb;
 
@@ -39,22 +40,13 @@ static_assert(sizeof(pomcp_pe_grid) == 1344, "pe grid layout");
 static_assert(sizeof(Line) == 128, "block line layout");
 static_assert(sizeof(OvfSlot) == 32, "overflow slot layout");
 
-struct pomcp_ctx {
+struct pomcp_ctx : HostCtx {
   pomcp_config cfg;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   DevParams dp{};
-  std::vector<void*> allocs;
-  std::string err;
   bool have_snapshot = false;
   TreeHdr* snap_hdr = nullptr;
   std::vector<int32_t> host_upd;
   std::vector<pomcp_root_stats> host_stats;
-  DrvModel host_drv;      // the configured environment's device tables
-  PeModel host_pe;
-  const void* host_model = nullptr;
-  size_t model_bytes = 0;
   pomcp_merged_root* merged = nullptr;   // [B] device results of pomcp_merge_roots
   double* gather = nullptr;              // [gather_world][B][R] pomcp_root_gather_buffer
   int gather_world = 0;
@@ -116,40 +108,29 @@ constexpr int64_t kWaveSearchMaxScratch = (int64_t)4 << 30;
 // step-tree producers for depth limits up to this (use_step_tree)
 constexpr int kStepTreeMaxDepth = 8;
 
-
-// Launch `KERNEL<Env>` for the context's environment.
-#define PB_ENV_LAUNCH(ctx, KERNEL, grid, block, ...)                                          \
-  do {                                                                                         \
-    if ((ctx)->dp.env == POMCP_ENV_PURSUIT_EVASION)                                            \
-      hipLaunchKernelGGL(KERNEL<EnvPursuitEvasion>, grid, block, 0, (ctx)->stream, __VA_ARGS__); \
-    else                                                                                       \
-      hipLaunchKernelGGL(KERNEL<EnvDriving>, grid, block, 0, (ctx)->stream, __VA_ARGS__);    \
-  } while (0)
-
-#define HIP_TRY(ctx, expr)                                                          \
-  do {                                                                              \
-    hipError_t e_ = (expr);                                                         \
-    if (e_ != hipSuccess) {                                                         \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e_);              \
-      return POMCP_E_HIP;                                                           \
-    }                                                                               \
-  } while (0)
-
-static int fail(pomcp_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
+// f(Env{}) with the context's environment (envs.h)
+template <class F>
+static void with_env(const pomcp_ctx* ctx, F&& f) {
+  env_dispatch<EnvDriving, EnvPursuitEvasion>(ctx->dp.env, f);
 }
 
-static int dev_alloc(pomcp_ctx* ctx, void** out, size_t bytes) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    ctx->err = "hipMalloc(" + std::to_string(bytes) + " B): " + hipGetErrorString(e);
-    return POMCP_E_HIP;
-  }
-  ctx->allocs.push_back(p);
-  *out = p;
-  return POMCP_OK;
+// f(Env{}) with the context's environment as the episode kernels know it (episode_step.h)
+template <class F>
+static void with_episode_env(const pomcp_ctx* ctx, F&& f) {
+  env_dispatch<EpDriving, EpPursuitEvasion>(ctx->dp.env, f);
+}
+
+// The first tree whose status code(t) is an error, named by its kind.
+template <class Code>
+static int first_tree_error(pomcp_ctx* ctx, const char* what, Code code) {
+  return first_error(ctx, ctx->dp.B, code, [&](int t, int e) {
+    const char* kind = e == POMCP_E_ARENA ? "arena capacity exceeded"
+                       : e == POMCP_E_NOT_FOUND ? "root has no child node for action"
+                       : e == POMCP_E_STATE ? "call out of order"
+                       : e == POMCP_E_INVALID ? "invalid observation"
+                                              : "error";
+    return std::string(what) + ": tree " + std::to_string(t) + ": " + kind;
+  });
 }
 
 static unsigned grid_blocks(int B) { return (unsigned)((B + kTreesPerBlock - 1) / kTreesPerBlock); }
@@ -240,46 +221,22 @@ static int validate(const pomcp_config* c, std::string* why) {
 int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomcp_ctx** out) {
   if (!cfg || !out) return POMCP_E_INVALID;
   *out = nullptr;
-  auto* ctx = new pomcp_ctx();
-  ctx->cfg = *cfg;
   std::string why;
   int rc = validate(cfg, &why);
   if (rc != POMCP_OK) {
     std::fprintf(stderr, "pomcp_create: %s\n", why.c_str());
+    return rc;
+  }
+  auto* ctx = new pomcp_ctx();
+  ctx->cfg = *cfg;
+  if ((rc = ctx->open(device, hip_stream)) != POMCP_OK) {
     delete ctx;
     return rc;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0) {
-    delete ctx;
-    return POMCP_E_NO_DEVICE;
-  }
-  ctx->device = device;
-  if (hipSetDevice(device) != hipSuccess) {
-    delete ctx;
-    return POMCP_E_NO_DEVICE;
-  }
-  if (hip_stream) {
-    ctx->stream = (hipStream_t)hip_stream;
-  } else {
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete ctx;
-      return POMCP_E_HIP;
-    }
-    ctx->own_stream = true;
-  }
   const pomcp_config& c = *cfg;
+  ctx->set_env_model(c);
   DevParams& d = ctx->dp;
   d.env = c.env_id;
-  if (c.env_id == POMCP_ENV_PURSUIT_EVASION) {
-    build_pe_model(c.pe_grid, &ctx->host_pe);
-    ctx->host_model = &ctx->host_pe;
-    ctx->model_bytes = sizeof(PeModel);
-  } else {
-    make_model(&c.grid, &ctx->host_drv);
-    ctx->host_model = &ctx->host_drv;
-    ctx->model_bytes = sizeof(DrvModel);
-  }
   d.B = c.num_trees;
   d.A = c.num_actions;
   d.ego = c.ego_agent;
@@ -309,42 +266,38 @@ int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomc
   d.tm = c.type_based;
   d.lines = blk_lines(d.A, d.tm);
   const int64_t B = c.num_trees;
-  void* p;
-#define ALLOC(field, type, count)                                               \
-  do {                                                                          \
-    if ((rc = dev_alloc(ctx, &p, sizeof(type) * (size_t)(count))) != POMCP_OK) {\
-      pomcp_destroy(ctx);                                                       \
-      return rc;                                                                \
-    }                                                                           \
-    d.field = reinterpret_cast<decltype(d.field)>(p);                           \
-  } while (0)
-  ALLOC(hdr, TreeHdr, B);
-  ALLOC(an, Line, arena_lines((int)B, d.Nb, d.lines));   // interleaved by search wave
-  ALLOC(ovf, OvfSlot, B * d.H);
+  // (the first failure skips the rest)
+  auto alloc = [&](auto*& field, int64_t count) {
+    if (rc == POMCP_OK) rc = ctx->alloc(field, (size_t)count);
+  };
+  alloc(d.hdr, B);
+  alloc(d.an, arena_lines((int)B, d.Nb, d.lines));   // interleaved by search wave
+  alloc(d.ovf, B * d.H);
   // pomcp_device.h WaveLog: 3 u32 arrays per search wave (+ aux when type-based)
-  ALLOC(plog, uint32_t, (int64_t)search_waves((int)B) * kWave * d.Np * (3 + d.tm));
-  if (d.tm) ALLOC(tmt, TmTables, 1);
-  ALLOC(wlog, uint32_t, search_waves((int)B));
-  ALLOC(want, uint32_t, B);
-  ALLOC(want_info, int4, B);
-  ALLOC(cnt, int32_t, B);
-  ALLOC(belief, uint4, B * d.Nr);
-  ALLOC(path, uint4, B * 3 * kMaxPath);
-  ALLOC(logtab, double, c.log_table_size);
-  ALLOC(dpow, double, c.discount_pow_size);
-  ALLOC(model, uint8_t, ctx->model_bytes);
-  ALLOC(stats, pomcp_root_stats, B);
-  ALLOC(merge, double, B * POMCP_XREC(d.A));
-  ALLOC(upd_out, int32_t, B * 2);
-  ALLOC(in_actions, int32_t, B);
-  ALLOC(in_obs, uint64_t, B);
-  ALLOC(out_obs, uint64_t, B);
-#undef ALLOC
-  if ((rc = dev_alloc(ctx, &p, sizeof(pomcp_merged_root) * (size_t)B)) != POMCP_OK) {
+  if (rc == POMCP_OK)
+    rc = ctx->alloc_bytes(d.plog, sizeof(uint32_t) * (size_t)((int64_t)search_waves((int)B) * kWave *
+                                                              d.Np * (3 + d.tm)));
+  if (d.tm) alloc(d.tmt, 1);
+  alloc(d.wlog, search_waves((int)B));
+  alloc(d.want, B);
+  alloc(d.want_info, B);
+  alloc(d.cnt, B);
+  alloc(d.belief, B * d.Nr);
+  alloc(d.path, B * 3 * kMaxPath);
+  alloc(d.logtab, c.log_table_size);
+  alloc(d.dpow, c.discount_pow_size);
+  if (rc == POMCP_OK) rc = ctx->alloc_bytes(d.model, ctx->model_bytes);
+  alloc(d.stats, B);
+  alloc(d.merge, B * POMCP_XREC(d.A));
+  alloc(d.upd_out, B * 2);
+  alloc(d.in_actions, B);
+  alloc(d.in_obs, B);
+  alloc(d.out_obs, B);
+  alloc(ctx->merged, B);
+  if (rc != POMCP_OK) {
     pomcp_destroy(ctx);
     return rc;
   }
-  ctx->merged = reinterpret_cast<pomcp_merged_root*>(p);
   d.logtab_n = c.log_table_size;
   d.dpow_n = (int32_t)(c.discount_pow_size > INT32_MAX ? INT32_MAX : c.discount_pow_size);
   hipStream_t s = ctx->stream;
@@ -352,12 +305,9 @@ int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomc
   if (hipMemsetAsync(d.ovf, 0, sizeof(OvfSlot) * (size_t)(B * d.H), s) != hipSuccess ||
       hipMemsetAsync(d.hdr, 0, sizeof(TreeHdr) * (size_t)B, s) != hipSuccess ||
       hipMemsetAsync(d.stats, 0, sizeof(pomcp_root_stats) * (size_t)B, s) != hipSuccess ||
-      hipMemcpyAsync((void*)d.logtab, c.log_table, sizeof(double) * c.log_table_size,
-                     hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync((void*)d.dpow, c.discount_pow, sizeof(double) * c.discount_pow_size,
-                     hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync((void*)d.model, ctx->host_model, ctx->model_bytes, hipMemcpyHostToDevice,
-                     s) != hipSuccess) {
+      ctx->upload(d.logtab, c.log_table, (size_t)c.log_table_size) != POMCP_OK ||
+      ctx->upload(d.dpow, c.discount_pow, (size_t)c.discount_pow_size) != POMCP_OK ||
+      ctx->upload_bytes(d.model, ctx->host_model, ctx->model_bytes) != POMCP_OK) {
     ctx->err = "initial upload failed";
     pomcp_destroy(ctx);
     return POMCP_E_HIP;
@@ -371,8 +321,7 @@ int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomc
   }
   // same stream as the zeroing memset above (the engine stream is non-blocking:
   // a null-stream copy would not be ordered after it)
-  if (hipMemcpyAsync(d.hdr, h.data(), sizeof(TreeHdr) * (size_t)B, hipMemcpyHostToDevice, s) !=
-      hipSuccess) {
+  if (ctx->upload(d.hdr, h.data(), (size_t)B) != POMCP_OK) {
     ctx->err = "header upload failed";
     pomcp_destroy(ctx);
     return POMCP_E_HIP;
@@ -396,21 +345,18 @@ int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomc
 
 void pomcp_destroy(pomcp_ctx* ctx) {
   if (!ctx) return;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (void* p : ctx->allocs) (void)hipFree(p);
+  ctx->close();
   if (ctx->snap_hdr) (void)hipFree(ctx->snap_hdr);
   for (hipEvent_t e : ctx->ep_ev)
     if (e) (void)hipEventDestroy(e);
-  if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
 int pomcp_reset(pomcp_ctx* ctx) {
   if (!ctx) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_reset, dim3(grid_blocks(ctx->dp.B)), dim3(256), 0, ctx->stream, ctx->dp);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   ctx->have_snapshot = false;
   ctx->defer_pending = false;
   ctx->have_root = false;
@@ -418,20 +364,8 @@ int pomcp_reset(pomcp_ctx* ctx) {
   return POMCP_OK;
 }
 
-static int first_tree_error(pomcp_ctx* ctx, const int32_t* codes, int stride, int off,
-                            const char* what) {
-  for (int t = 0; t < ctx->dp.B; ++t) {
-    const int e = codes[(size_t)t * stride + off];
-    if (e != 0) {
-      const char* kind = e == POMCP_E_ARENA ? "arena capacity exceeded"
-                         : e == POMCP_E_NOT_FOUND ? "root has no child node for action"
-                         : e == POMCP_E_STATE ? "call out of order"
-                         : e == POMCP_E_INVALID ? "invalid observation"
-                                                : "error";
-      return fail(ctx, e, std::string(what) + ": tree " + std::to_string(t) + ": " + kind);
-    }
-  }
-  return POMCP_OK;
+static int first_update_error(pomcp_ctx* ctx) {   // host_upd: [B][2] {root_abs, error}
+  return first_tree_error(ctx, "update", [&](int t) { return ctx->host_upd[2 * (size_t)t + 1]; });
 }
 
 // Scratch of the subtree compaction (k_compact), allocated on the first
@@ -441,32 +375,23 @@ static int ensure_compaction_scratch(pomcp_ctx* ctx) {
   DevParams& d = ctx->dp;
   if (d.cmap) return POMCP_OK;
   const int64_t B = d.B;
-  void* p = nullptr;
-  int rc;
-  if ((rc = dev_alloc(ctx, &p, sizeof(int32_t) * (size_t)(B * d.Nb))) != POMCP_OK) return rc;
-  d.cmap = reinterpret_cast<int32_t*>(p);
-  if ((rc = dev_alloc(ctx, &p, sizeof(int32_t) * (size_t)(B * d.Nb))) != POMCP_OK) return rc;
-  d.cpar = reinterpret_cast<int32_t*>(p);
-  if ((rc = dev_alloc(ctx, &p, sizeof(int32_t) * (size_t)(B * d.H))) != POMCP_OK) return rc;
-  d.ovf_new = reinterpret_cast<int32_t*>(p);
-  if ((rc = dev_alloc(ctx, &p, sizeof(OvfSlot) * (size_t)(B * d.H))) != POMCP_OK) return rc;
-  d.ovf_tmp = reinterpret_cast<OvfSlot*>(p);
-  if ((rc = dev_alloc(ctx, &p, sizeof(uint4) * (size_t)B)) != POMCP_OK) return rc;
-  d.scan_info = reinterpret_cast<uint4*>(p);
   // the streaming scan's look-back records: every wave log's capacity in
   // segments; zeroed (tag epoch 0 is never current)
   const int waves = search_waves((int)B);
   d.lf_nseg = (int32_t)((kWave * d.Np + kLfSeg - 1) / kLfSeg);
-  const size_t nd = sizeof(LfDesc) * (size_t)waves * (size_t)((d.lf_nseg + kLfChunk - 1) / kLfChunk);
-  if ((rc = dev_alloc(ctx, &p, nd)) != POMCP_OK) return rc;
-  d.lf_desc = reinterpret_cast<LfDesc*>(p);
-  if ((rc = dev_alloc(ctx, &p, 2 * sizeof(uint32_t))) != POMCP_OK) return rc;
-  d.lf_fail = reinterpret_cast<uint32_t*>(p);
-  if ((rc = dev_alloc(ctx, &p, sizeof(int16_t) * (size_t)waves * kCm16)) != POMCP_OK) return rc;
-  d.cm16 = reinterpret_cast<int16_t*>(p);
-  if ((rc = dev_alloc(ctx, &p, sizeof(int32_t) * (size_t)waves * kCm16Off)) != POMCP_OK) return rc;
-  d.cm16_off = reinterpret_cast<int32_t*>(p);
-  HIP_TRY(ctx, hipMemsetAsync(d.lf_desc, 0, nd, ctx->stream));
+  const size_t nd = (size_t)waves * (size_t)((d.lf_nseg + kLfChunk - 1) / kLfChunk);
+  int rc;
+  if ((rc = ctx->alloc(d.cmap, (size_t)(B * d.Nb))) != POMCP_OK ||
+      (rc = ctx->alloc(d.cpar, (size_t)(B * d.Nb))) != POMCP_OK ||
+      (rc = ctx->alloc(d.ovf_new, (size_t)(B * d.H))) != POMCP_OK ||
+      (rc = ctx->alloc(d.ovf_tmp, (size_t)(B * d.H))) != POMCP_OK ||
+      (rc = ctx->alloc(d.scan_info, (size_t)B)) != POMCP_OK ||
+      (rc = ctx->alloc(d.lf_desc, nd)) != POMCP_OK ||
+      (rc = ctx->alloc(d.lf_fail, 2)) != POMCP_OK ||
+      (rc = ctx->alloc(d.cm16, (size_t)waves * kCm16)) != POMCP_OK ||
+      (rc = ctx->alloc(d.cm16_off, (size_t)waves * kCm16Off)) != POMCP_OK)
+    return rc;
+  PB_TRY(ctx, hipMemsetAsync(d.lf_desc, 0, sizeof(LfDesc) * nd, ctx->stream));
   ctx->lf_epoch = 0;
   const char* ls = std::getenv("POMCP_LOG_SCAN");
   ctx->log_scan_legacy = ls != nullptr && std::string(ls) == "legacy";
@@ -476,12 +401,12 @@ static int ensure_compaction_scratch(pomcp_ctx* ctx) {
   ctx->lf_packed_cmap = !(pk != nullptr && std::string(pk) == "off");
   // the persistent grid: as many workgroups as are resident at once
   int per_cu = 0, ncu = 0;
-  HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                   &per_cu, reinterpret_cast<const void*>(d.env == POMCP_ENV_PURSUIT_EVASION
-                                                              ? &k_log_filter<EnvPursuitEvasion>
-                                                              : &k_log_filter<EnvDriving>),
-                   kLfThreads, 0));
-  HIP_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
+  PB_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                  &per_cu, reinterpret_cast<const void*>(d.env == POMCP_ENV_PURSUIT_EVASION
+                                                             ? &k_log_filter<EnvPursuitEvasion>
+                                                             : &k_log_filter<EnvDriving>),
+                  kLfThreads, 0));
+  PB_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
   ctx->lf_grid = (per_cu > 0 ? per_cu : 1) * (ncu > 0 ? ncu : 1);
   return POMCP_OK;
 }
@@ -496,45 +421,52 @@ static int launch_update(pomcp_ctx* ctx, bool reroot) {
   // (re-roots only: an initial update leaves an empty arena) with one ordered
   // scan of each search wave's log that also extracts the child's particles;
   // then the per-tree update (initial belief / new root + reinvigoration)
-  PB_ENV_LAUNCH(ctx, k_reroot_child, dim3(grid_blocks(B)), dim3(256), ctx->dp);
-  HIP_TRY(ctx, hipGetLastError());
+  with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_reroot_child<decltype(e)>, dim3(grid_blocks(B)), dim3(256), 0, ctx->stream,
+                       ctx->dp);
+  });
+  PB_TRY(ctx, hipGetLastError());
   if (reroot) {
     int rc = ensure_compaction_scratch(ctx);
     if (rc != POMCP_OK) return rc;
     hipLaunchKernelGGL(k_compact, dim3(grid_blocks(B)), dim3(256), 0, ctx->stream, ctx->dp);
-    HIP_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipGetLastError());
     if (ctx->log_scan_legacy) {
-      PB_ENV_LAUNCH(ctx, k_compact_log, dim3((unsigned)search_waves(B)), dim3(64 * kLogWaves),
-                    ctx->dp);
+      with_env(ctx, [&](auto e) {
+        hipLaunchKernelGGL(k_compact_log<decltype(e)>, dim3((unsigned)search_waves(B)),
+                           dim3(64 * kLogWaves), 0, ctx->stream, ctx->dp);
+      });
     } else {
       // the streaming scan: the filter over every log's segments, then the
       // materialising pass over the kept records
       if (++ctx->lf_epoch >= (1u << 30)) {   // (tags hold 30 bits: start over on zeroed records)
-        HIP_TRY(ctx, hipMemsetAsync(ctx->dp.lf_desc, 0,
-                                    sizeof(LfDesc) * (size_t)search_waves(B) *
-                                        (size_t)((ctx->dp.lf_nseg + kLfChunk - 1) / kLfChunk),
-                                    ctx->stream));
+        PB_TRY(ctx, hipMemsetAsync(ctx->dp.lf_desc, 0,
+                                   sizeof(LfDesc) * (size_t)search_waves(B) *
+                                       (size_t)((ctx->dp.lf_nseg + kLfChunk - 1) / kLfChunk),
+                                   ctx->stream));
         ctx->lf_epoch = 1;
       }
       ctx->dp.lf_epoch = ctx->lf_epoch;
-      HIP_TRY(ctx, hipMemsetAsync(ctx->dp.lf_fail, 0, 2 * sizeof(uint32_t), ctx->stream));
+      PB_TRY(ctx, hipMemsetAsync(ctx->dp.lf_fail, 0, 2 * sizeof(uint32_t), ctx->stream));
       hipLaunchKernelGGL(k_pack_cmap, dim3((unsigned)search_waves(B)), dim3(256), 0, ctx->stream, ctx->dp,
                          ctx->lf_packed_cmap ? 1 : 0);
-      HIP_TRY(ctx, hipGetLastError());
-      PB_ENV_LAUNCH(ctx, k_log_filter, dim3((unsigned)ctx->lf_grid), dim3(kLfThreads), ctx->dp,
-                    search_waves(B));
-      HIP_TRY(ctx, hipGetLastError());
-      if (ctx->dp.env == POMCP_ENV_PURSUIT_EVASION)
-        hipLaunchKernelGGL((k_compact_log<EnvPursuitEvasion, true>), dim3((unsigned)search_waves(B)),
+      PB_TRY(ctx, hipGetLastError());
+      with_env(ctx, [&](auto e) {
+        hipLaunchKernelGGL(k_log_filter<decltype(e)>, dim3((unsigned)ctx->lf_grid), dim3(kLfThreads), 0,
+                           ctx->stream, ctx->dp, search_waves(B));
+      });
+      PB_TRY(ctx, hipGetLastError());
+      with_env(ctx, [&](auto e) {
+        hipLaunchKernelGGL((k_compact_log<decltype(e), true>), dim3((unsigned)search_waves(B)),
                            dim3(64 * kMatWaves), 0, ctx->stream, ctx->dp);
-      else
-        hipLaunchKernelGGL((k_compact_log<EnvDriving, true>), dim3((unsigned)search_waves(B)),
-                           dim3(64 * kMatWaves), 0, ctx->stream, ctx->dp);
+      });
     }
-    HIP_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipGetLastError());
   }
-  PB_ENV_LAUNCH(ctx, k_update, dim3(grid_blocks(B)), dim3(256), ctx->dp);
-  HIP_TRY(ctx, hipGetLastError());
+  with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_update<decltype(e)>, dim3(grid_blocks(B)), dim3(256), 0, ctx->stream, ctx->dp);
+  });
+  PB_TRY(ctx, hipGetLastError());
   return POMCP_OK;
 }
 
@@ -542,31 +474,30 @@ int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_key
                  int32_t* root_absorbing_out) {
   if (!ctx || !obs_keys) return POMCP_E_INVALID;
   if (ctx->dp.tm && !ctx->tm_set) return fail(ctx, POMCP_E_STATE, "update: pomcp_set_type_policies first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
   std::vector<int32_t> acts((size_t)B, -1);
   if (actions) std::memcpy(acts.data(), actions, sizeof(int32_t) * (size_t)B);
-  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_actions, acts.data(), sizeof(int32_t) * B,
-                              hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_obs, obs_keys, sizeof(uint64_t) * B,
-                              hipMemcpyHostToDevice, ctx->stream));
+  int rc;
+  if ((rc = ctx->upload(ctx->dp.in_actions, acts.data(), (size_t)B)) != POMCP_OK ||
+      (rc = ctx->upload(ctx->dp.in_obs, obs_keys, (size_t)B)) != POMCP_OK)
+    return rc;
   bool reroot = false;
   for (int t = 0; t < B && !reroot; ++t) reroot = acts[t] >= 0;
-  const int rc = launch_update(ctx, reroot);
-  if (rc != POMCP_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->host_upd.data(), ctx->dp.upd_out, sizeof(int32_t) * 2 * B,
-                              hipMemcpyDeviceToHost, ctx->stream));
+  if ((rc = launch_update(ctx, reroot)) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipMemcpyAsync(ctx->host_upd.data(), ctx->dp.upd_out, sizeof(int32_t) * 2 * B,
+                             hipMemcpyDeviceToHost, ctx->stream));
   uint32_t lf_fail = 0u;
   if (reroot && !ctx->log_scan_legacy)
-    HIP_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    PB_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
   ctx->defer_pending = false;   // k_compact_log materialised the surviving deferred children
   ctx->have_root = true;
   if (root_absorbing_out)
     for (int t = 0; t < B; ++t) root_absorbing_out[t] = ctx->host_upd[2 * t];
-  return first_tree_error(ctx, ctx->host_upd.data(), 2, 1, "update");
+  return first_update_error(ctx);
 }
 
 static bool wave_search_fits(const pomcp_ctx* ctx) {
@@ -626,10 +557,8 @@ static bool use_step_tree(const pomcp_ctx* ctx) {
 
 static int launch_search_wave(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   if (!ctx->dp.lscr) {   // the per-tree scratch log, on first use
-    void* q = nullptr;
-    int rc = dev_alloc(ctx, &q, sizeof(LogRec) * (size_t)ctx->dp.B * (size_t)ctx->dp.Np);
+    const int rc = ctx->alloc(ctx->dp.lscr, (size_t)ctx->dp.B * (size_t)ctx->dp.Np);
     if (rc != POMCP_OK) return rc;
-    ctx->dp.lscr = reinterpret_cast<LogRec*>(q);
   }
   using KFn = void (*)(DevParams, int, int);
 #define PB_LDS_ROW(NP)                                                                          \
@@ -645,14 +574,14 @@ static int launch_search_wave(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   hipLaunchKernelGGL(table[spec][e][ctx->dp.sel], dim3((unsigned)ctx->dp.B),
                      dim3((unsigned)(kWave * (1 + spec * kSpecProducers))), 0, ctx->stream, ctx->dp,
                      (int)num_sims, final_sel);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   const int nsw = search_waves(ctx->dp.B);
   hipLaunchKernelGGL(k_log_merge, dim3((unsigned)(ctx->dp.B < kWave ? ctx->dp.B : kWave), (unsigned)nsw),
                      dim3(256), 0, ctx->stream, ctx->dp);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_log_merge_end, dim3((unsigned)((nsw + 63) / 64)), dim3(64), 0, ctx->stream,
                      ctx->dp, nsw);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   return POMCP_OK;
 }
 
@@ -675,7 +604,7 @@ int pomcp_debug_search_depth_spec(const pomcp_ctx* ctx) {
 static int launch_search(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   if (!ctx || num_sims < 0) return POMCP_E_INVALID;
   if (ctx->dp.tm && !ctx->tm_set) return fail(ctx, POMCP_E_STATE, "search: pomcp_set_type_policies first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   if (resolve_search_kind(ctx) == POMCP_SEARCH_WAVE) return launch_search_wave(ctx, num_sims, final_sel);
   const int tpb = search_tpb(ctx->dp.B);
   const dim3 grid((unsigned)((ctx->dp.B + tpb - 1) / tpb)), block((unsigned)tpb);
@@ -685,8 +614,8 @@ static int launch_search(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   int sims = (int)num_sims, fsel = final_sel;
   void* args[] = {&ctx->dp, &sims, &fsel};
   const int dl = search_depth_spec(ctx);
-  HIP_TRY(ctx, hipLaunchKernel(pb_search_kernel(row, e, ctx->dp.sel, dl), grid, block, args, 0, ctx->stream));
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipLaunchKernel(pb_search_kernel(row, e, ctx->dp.sel, dl), grid, block, args, 0, ctx->stream));
+  PB_TRY(ctx, hipGetLastError());
   if (ctx->dp.defer && !ctx->dp.tm && num_sims > 0) ctx->defer_pending = true;
   return POMCP_OK;
 }
@@ -704,17 +633,16 @@ int pomcp_search_continue(pomcp_ctx* ctx, int32_t num_sims) { return launch_sear
 
 int pomcp_get_root_stats(pomcp_ctx* ctx, pomcp_root_stats* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->dp.stats, sizeof(pomcp_root_stats) * ctx->dp.B,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (int t = 0; t < ctx->dp.B; ++t)
-    if (out[t].error != 0) {
-      std::vector<int32_t> codes((size_t)ctx->dp.B);
-      for (int k = 0; k < ctx->dp.B; ++k) codes[k] = out[k].error;
-      return first_tree_error(ctx, codes.data(), 1, 0, "search");
-    }
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  const int rc = ctx->fetch(out, ctx->dp.stats, (size_t)ctx->dp.B);
+  if (rc != POMCP_OK) return rc;
+  return first_tree_error(ctx, "search", [&](int t) { return out[t].error; });
+}
+
+// One tree's header, from the device.
+static int fetch_hdr(pomcp_ctx* ctx, int32_t tree, TreeHdr* h) {
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(h, ctx->dp.hdr + tree, 1);
 }
 
 int pomcp_set_root_belief(pomcp_ctx* ctx, int32_t tree, const uint32_t* particles, int32_t count) {
@@ -728,11 +656,9 @@ int pomcp_set_root_belief(pomcp_ctx* ctx, int32_t tree, const uint32_t* particle
   for (int32_t i = 0; i < count; ++i)
     if (particles[3 * i] != t || t < 1u)
       return fail(ctx, POMCP_E_INVALID, "set_root_belief: every particle needs the same t >= 1");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   TreeHdr h;
-  HIP_TRY(ctx, hipMemcpyAsync(&h, ctx->dp.hdr + tree, sizeof(TreeHdr), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = fetch_hdr(ctx, tree, &h);
+  if (rc != POMCP_OK) return rc;
   if (h.root_t != 0 || h.n_blocks != 0 || h.error != 0)
     return fail(ctx, POMCP_E_STATE, "set_root_belief: the tree must be fresh (pomcp_reset)");
   // the region's records [at, at + count) in memory order (bel_at: the end of
@@ -743,9 +669,8 @@ int pomcp_set_root_belief(pomcp_ctx* ctx, int32_t tree, const uint32_t* particle
   for (int32_t i = 0; i < count; ++i)
     b[bel_at(sel, ctx->dp.Nr, i) - at] =
         make_uint4(particles[3 * i], particles[3 * i + 1], particles[3 * i + 2], 0u);
-  uint4* dst = ctx->dp.belief + (int64_t)tree * ctx->dp.Nr + at;
-  HIP_TRY(ctx, hipMemcpyAsync(dst, b.data(), sizeof(uint4) * (size_t)count, hipMemcpyHostToDevice,
-                              ctx->stream));
+  rc = ctx->upload(ctx->dp.belief + (int64_t)tree * ctx->dp.Nr + at, b.data(), (size_t)count);
+  if (rc != POMCP_OK) return rc;
   h.belief_sel = sel;
   h.belief_size = count;
   h.root_t = (int32_t)t;
@@ -754,9 +679,8 @@ int pomcp_set_root_belief(pomcp_ctx* ctx, int32_t tree, const uint32_t* particle
   h.root_visits = 0;
   h.root_abs = 0;
   h.n_nodes += 1;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->dp.hdr + tree, &h, sizeof(TreeHdr), hipMemcpyHostToDevice,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = ctx->upload(ctx->dp.hdr + tree, &h, 1)) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_root = true;
   return POMCP_OK;
 }
@@ -767,9 +691,8 @@ static int read_root_belief(pomcp_ctx* ctx, int32_t tree, const TreeHdr& h, int 
   const int sel = h.belief_sel;
   const int64_t at = sel ? ctx->dp.Nr - n : 0;
   std::vector<uint4> raw((size_t)n);
-  HIP_TRY(ctx, hipMemcpyAsync(raw.data(), ctx->dp.belief + (int64_t)tree * ctx->dp.Nr + at,
-                              sizeof(uint4) * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int rc = ctx->fetch(raw.data(), ctx->dp.belief + (int64_t)tree * ctx->dp.Nr + at, (size_t)n);
+  if (rc != POMCP_OK) return rc;
   for (int i = 0; i < n; ++i) out[i] = raw[bel_at(sel, ctx->dp.Nr, i) - at];
   return POMCP_OK;
 }
@@ -777,19 +700,14 @@ static int read_root_belief(pomcp_ctx* ctx, int32_t tree, const TreeHdr& h, int 
 int pomcp_get_root_belief(pomcp_ctx* ctx, int32_t tree, uint32_t* out, int32_t capacity,
                           int32_t* count) {
   if (!ctx || !count || tree < 0 || tree >= ctx->dp.B) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   TreeHdr h;
-  HIP_TRY(ctx, hipMemcpyAsync(&h, ctx->dp.hdr + tree, sizeof(TreeHdr), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = fetch_hdr(ctx, tree, &h);
+  if (rc != POMCP_OK) return rc;
   *count = h.belief_size;
   if (!out || capacity <= 0) return POMCP_OK;
   const int n = h.belief_size < capacity ? h.belief_size : capacity;
   std::vector<uint4> tmp((size_t)n);
-  if (n > 0) {
-    int rc = read_root_belief(ctx, tree, h, n, tmp.data());
-    if (rc != POMCP_OK) return rc;
-  }
+  if ((rc = read_root_belief(ctx, tree, h, n, tmp.data())) != POMCP_OK) return rc;
   for (int i = 0; i < n; ++i) {
     out[3 * i + 0] = tmp[i].x;
     out[3 * i + 1] = tmp[i].y;
@@ -846,14 +764,14 @@ int pomcp_set_type_policies(pomcp_ctx* ctx, const pomcp_type_policies* tp) {
     }
     cum(tp->meta_weight[j], m, t.meta_cum[j], &t.meta_tot[j]);
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   ctx->host_tm = t;
   std::memset(ctx->host_other_pi, 0, sizeof(ctx->host_other_pi));
   for (int j = 0; j < no; ++j)
     for (int a = 0; a < A; ++a) ctx->host_other_pi[j][a] = tp->other_pi[j][a];
-  HIP_TRY(ctx, hipMemcpyAsync(const_cast<TmTables*>(ctx->dp.tmt), &ctx->host_tm, sizeof(TmTables),
-                              hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int rc = ctx->upload(ctx->dp.tmt, &ctx->host_tm, 1);
+  if (rc != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->tm_set = true;
   return POMCP_OK;
 }
@@ -861,11 +779,9 @@ int pomcp_set_type_policies(pomcp_ctx* ctx, const pomcp_type_policies* tp) {
 int pomcp_get_root_prior(pomcp_ctx* ctx, int32_t tree, double* out) {
   if (!ctx || !out || tree < 0 || tree >= ctx->dp.B) return POMCP_E_INVALID;
   if (!ctx->dp.tm) return fail(ctx, POMCP_E_STATE, "get_root_prior: context is not type_based");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   TreeHdr h;
-  HIP_TRY(ctx, hipMemcpyAsync(&h, ctx->dp.hdr + tree, sizeof(TreeHdr), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = fetch_hdr(ctx, tree, &h);
+  if (rc != POMCP_OK) return rc;
   const int A = ctx->dp.A;
   if (h.root_blk < 0) {   // no block yet: the prior its code names
     const int code = h.root_code >= 0 && h.root_code <= kTmMax ? h.root_code : 0;
@@ -874,31 +790,31 @@ int pomcp_get_root_prior(pomcp_ctx* ctx, int32_t tree, double* out) {
   }
   const Line* blk = ctx->dp.an + tree_base_lines(tree, ctx->dp.Nb, ctx->dp.lines) +
                     (int64_t)h.root_blk * blk_stride_lines(ctx->dp.lines);
-  HIP_TRY(ctx, hipMemcpyAsync(out, reinterpret_cast<const uint4*>(blk) + part_prior(A),
-                              sizeof(double) * A, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  const uint4* prior = reinterpret_cast<const uint4*>(blk) + part_prior(A);
+  return ctx->fetch(out, reinterpret_cast<const double*>(prior), (size_t)A);
 }
 
 int pomcp_get_root_policies(pomcp_ctx* ctx, int32_t tree, int32_t* out, int32_t capacity,
                             int32_t* count) {
   if (!ctx || !count || tree < 0 || tree >= ctx->dp.B) return POMCP_E_INVALID;
   if (!ctx->dp.tm) return fail(ctx, POMCP_E_STATE, "get_root_policies: context is not type_based");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   TreeHdr h;
-  HIP_TRY(ctx, hipMemcpyAsync(&h, ctx->dp.hdr + tree, sizeof(TreeHdr), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = fetch_hdr(ctx, tree, &h);
+  if (rc != POMCP_OK) return rc;
   *count = h.belief_size;
   if (!out || capacity <= 0) return POMCP_OK;
   const int n = h.belief_size < capacity ? h.belief_size : capacity;
   std::vector<uint4> tmp((size_t)n);
-  if (n > 0) {
-    int rc = read_root_belief(ctx, tree, h, n, tmp.data());
-    if (rc != POMCP_OK) return rc;
-  }
+  if ((rc = read_root_belief(ctx, tree, h, n, tmp.data())) != POMCP_OK) return rc;
   for (int i = 0; i < n; ++i) out[i] = (int32_t)tmp[i].w;
   return POMCP_OK;
+}
+
+// The query-state buffer of pomcp_belief_stats and its results, on first use.
+static int ensure_belief_buffers(pomcp_ctx* ctx) {
+  if (ctx->bel_out) return POMCP_OK;
+  const int rc = ctx->alloc(ctx->bel_out, (size_t)ctx->dp.B);
+  return rc != POMCP_OK ? rc : ctx->alloc(ctx->bel_q, (size_t)ctx->dp.B);
 }
 
 // k_belief_stats on the context stream (belief_stats.hip): one workgroup per
@@ -907,24 +823,17 @@ int pomcp_get_root_policies(pomcp_ctx* ctx, int32_t tree, int32_t* out, int32_t 
 // ctx->bel_out.
 static int launch_belief_stats(pomcp_ctx* ctx, const uint32_t* states, bool upload = true) {
   const int B = ctx->dp.B;
-  if (!ctx->bel_out) {
-    void* p = nullptr;
-    int rc = dev_alloc(ctx, &p, sizeof(pomcp_belief_counts) * (size_t)B);
-    if (rc != POMCP_OK) return rc;
-    ctx->bel_out = reinterpret_cast<pomcp_belief_counts*>(p);
-    rc = dev_alloc(ctx, &p, sizeof(uint2) * (size_t)B);
-    if (rc != POMCP_OK) return rc;
-    ctx->bel_q = reinterpret_cast<uint2*>(p);
-  }
-  if (states && upload)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->bel_q, states, sizeof(uint2) * (size_t)B,
-                                hipMemcpyHostToDevice, ctx->stream));
+  int rc = ensure_belief_buffers(ctx);
+  if (rc != POMCP_OK) return rc;
+  if (states && upload &&
+      (rc = ctx->upload(ctx->bel_q, reinterpret_cast<const uint2*>(states), (size_t)B)) != POMCP_OK)
+    return rc;
   const int num_other = ctx->dp.tm ? ctx->host_tm.n_other : 0;
   hipLaunchKernelGGL(k_belief_stats, dim3((unsigned)(B < kBelMaxGrid ? B : kBelMaxGrid)),
                      dim3(kBelThreads), 0, ctx->stream, ctx->dp,
                      states ? (const uint2*)ctx->bel_q : (const uint2*)nullptr, num_other,
                      ctx->bel_out);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   return POMCP_OK;
 }
 
@@ -940,28 +849,22 @@ int pomcp_belief_stats(pomcp_ctx* ctx, const uint32_t* states, pomcp_belief_coun
   if (!ctx || !out) return fail(ctx, POMCP_E_INVALID, "belief_stats: null argument");
   int rc = belief_stats_ready(ctx);
   if (rc != POMCP_OK) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   rc = launch_belief_stats(ctx, states);
   if (rc != POMCP_OK) return rc;
-  const int B = ctx->dp.B;
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->bel_out, sizeof(pomcp_belief_counts) * (size_t)B,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (int t = 0; t < B; ++t)
-    if (out[t].error != 0)
-      return fail(ctx, out[t].error, "belief_stats: tree " + std::to_string(t) + ": error " +
-                                         std::to_string(out[t].error) +
-                                         " (its own, or a particle's policy index out of range)");
-  return POMCP_OK;
+  if ((rc = ctx->fetch(out, ctx->bel_out, (size_t)ctx->dp.B)) != POMCP_OK) return rc;
+  return first_error(ctx, ctx->dp.B, [&](int t) { return out[t].error; }, [](int t, int e) {
+    return "belief_stats: tree " + std::to_string(t) + ": error " + std::to_string(e) +
+           " (its own, or a particle's policy index out of range)";
+  });
 }
 
 int pomcp_arena_usage(pomcp_ctx* ctx, int32_t* max_blocks_used, int32_t* max_log_used) {
   if (!ctx || !max_blocks_used || !max_log_used) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<TreeHdr> h((size_t)ctx->dp.B);
-  HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->dp.hdr, sizeof(TreeHdr) * h.size(),
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = ctx->fetch(h.data(), ctx->dp.hdr, h.size());
+  if (rc != POMCP_OK) return rc;
   int32_t nb = 0, nl = 0;
   for (const auto& x : h) {
     nb = x.n_blocks > nb ? x.n_blocks : nb;
@@ -974,15 +877,13 @@ int pomcp_arena_usage(pomcp_ctx* ctx, int32_t* max_blocks_used, int32_t* max_log
 
 int pomcp_rekey(pomcp_ctx* ctx, uint64_t seed) {
   if (!ctx) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<TreeHdr> h((size_t)ctx->dp.B);
-  HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->dp.hdr, sizeof(TreeHdr) * h.size(),
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = ctx->fetch(h.data(), ctx->dp.hdr, h.size());
+  if (rc != POMCP_OK) return rc;
   for (auto& x : h) x.seed = seed;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->dp.hdr, h.data(), sizeof(TreeHdr) * h.size(),
-                              hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if ((rc = ctx->upload(ctx->dp.hdr, h.data(), h.size())) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return POMCP_OK;
 }
 
@@ -995,8 +896,8 @@ int pomcp_root_merge_buffer(pomcp_ctx* ctx, void** device_ptr) {
 int pomcp_root_gather_buffer(pomcp_ctx* ctx, int32_t world, void** device_ptr) {
   if (!ctx || !device_ptr || world < 1) return POMCP_E_INVALID;
   if (world > ctx->gather_world) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    PB_TRY(ctx, hipSetDevice(ctx->device));
+    PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->gather) {
       for (auto& q : ctx->allocs)
         if (q == ctx->gather) q = nullptr;
@@ -1004,12 +905,10 @@ int pomcp_root_gather_buffer(pomcp_ctx* ctx, int32_t world, void** device_ptr) {
       ctx->gather = nullptr;
       ctx->gather_world = 0;
     }
-    void* q = nullptr;
-    const size_t bytes = sizeof(double) * (size_t)world * (size_t)ctx->dp.B * POMCP_XREC(ctx->dp.A);
-    int rc = dev_alloc(ctx, &q, bytes);
+    const size_t n = (size_t)world * (size_t)ctx->dp.B * POMCP_XREC(ctx->dp.A);
+    const int rc = ctx->alloc(ctx->gather, n);
     if (rc != POMCP_OK) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(q, 0, bytes, ctx->stream));
-    ctx->gather = reinterpret_cast<double*>(q);
+    PB_TRY(ctx, hipMemsetAsync(ctx->gather, 0, sizeof(double) * n, ctx->stream));
     ctx->gather_world = world;
   }
   *device_ptr = ctx->gather;
@@ -1032,7 +931,7 @@ static pb_nccl_allgather_fn pb_rccl_allgather() {
 
 int pomcp_allgather_root(pomcp_ctx* ctx, void* rccl_comm, int32_t world) {
   if (!ctx || !rccl_comm || world < 1) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const pb_nccl_allgather_fn allgather = pb_rccl_allgather();
   if (!allgather)
     return fail(ctx, POMCP_E_UNSUPPORTED,
@@ -1055,73 +954,65 @@ int pomcp_merge_roots(pomcp_ctx* ctx, int32_t group, int32_t world, pomcp_merged
     return fail(ctx, POMCP_E_INVALID, "merge_roots: no gather buffer for that many ranks");
   if ((int64_t)(world > 0 ? world : 1) * group > INT32_MAX / 2)
     return fail(ctx, POMCP_E_INVALID, "merge_roots: too many replicas");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int G = ctx->dp.B / group;
   const double* src = world > 0 ? ctx->gather : ctx->dp.merge;
   hipLaunchKernelGGL(k_merge_roots, dim3((unsigned)G), dim3(kWave), 0, ctx->stream, src,
                      (int)ctx->dp.B, (int)ctx->dp.A, (int)ctx->dp.sel, (int)group,
                      world > 0 ? (int)world : 1, ctx->merged);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   if (!out) return POMCP_OK;
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->merged, sizeof(pomcp_merged_root) * (size_t)G,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (int g = 0; g < G; ++g)
-    if (out[g].error != 0)
-      return fail(ctx, out[g].error, "search: planner " + std::to_string(g) + ": replica error " +
-                                         std::to_string(out[g].error));
-  return POMCP_OK;
+  const int rc = ctx->fetch(out, ctx->merged, (size_t)G);
+  if (rc != POMCP_OK) return rc;
+  return first_error(ctx, G, [&](int g) { return out[g].error; }, [](int g, int e) {
+    return "search: planner " + std::to_string(g) + ": replica error " + std::to_string(e);
+  });
 }
 
 int pomcp_synthetic_obs(pomcp_ctx* ctx, uint64_t env_seed_base, uint64_t* obs_keys_out) {
   if (!ctx) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  PB_ENV_LAUNCH(ctx, k_synthetic_obs, dim3(grid_blocks(ctx->dp.B)), dim3(256), ctx->dp,
-                env_seed_base);
-  HIP_TRY(ctx, hipGetLastError());
-  if (obs_keys_out) {
-    HIP_TRY(ctx, hipMemcpyAsync(obs_keys_out, ctx->dp.out_obs, sizeof(uint64_t) * ctx->dp.B,
-                                hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_synthetic_obs<decltype(e)>, dim3(grid_blocks(ctx->dp.B)), dim3(256), 0,
+                       ctx->stream, ctx->dp, env_seed_base);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  return obs_keys_out ? ctx->fetch(obs_keys_out, ctx->dp.out_obs, (size_t)ctx->dp.B) : POMCP_OK;
 }
 
 int pomcp_synthetic_step(pomcp_ctx* ctx, uint64_t env_seed_base, const int32_t* actions,
                          uint64_t* obs_keys_out) {
   if (!ctx || !actions) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
-  HIP_TRY(ctx, hipMemcpyAsync((void*)ctx->dp.in_actions, actions, sizeof(int32_t) * B,
-                              hipMemcpyHostToDevice, ctx->stream));
-  PB_ENV_LAUNCH(ctx, k_synthetic_step, dim3(grid_blocks(B)), dim3(256), ctx->dp, env_seed_base);
-  HIP_TRY(ctx, hipGetLastError());
-  if (obs_keys_out) {
-    HIP_TRY(ctx, hipMemcpyAsync(obs_keys_out, ctx->dp.out_obs, sizeof(uint64_t) * B,
-                                hipMemcpyDeviceToHost, ctx->stream));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const int rc = ctx->upload(ctx->dp.in_actions, actions, (size_t)B);
+  if (rc != POMCP_OK) return rc;
+  with_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_synthetic_step<decltype(e)>, dim3(grid_blocks(B)), dim3(256), 0, ctx->stream,
+                       ctx->dp, env_seed_base);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  if (obs_keys_out) return ctx->fetch(obs_keys_out, ctx->dp.out_obs, (size_t)B);
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (`actions` is the caller's memory)
   return POMCP_OK;
 }
 
 int pomcp_snapshot(pomcp_ctx* ctx) {
   if (!ctx) return POMCP_E_INVALID;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
   std::vector<TreeHdr> h((size_t)B);
-  HIP_TRY(ctx, hipMemcpyAsync(h.data(), ctx->dp.hdr, sizeof(TreeHdr) * B, hipMemcpyDeviceToHost,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = ctx->fetch(h.data(), ctx->dp.hdr, h.size());
+  if (rc != POMCP_OK) return rc;
   for (int t = 0; t < B; ++t) {
     // only the post-initial-update state (no blocks, no log, empty overflow map)
     // is restorable by resetting the header and bumping the map generation
     if (h[t].root_t != 1 || h[t].n_blocks != 0 || h[t].n_log != 0 || h[t].error != 0)
       return fail(ctx, POMCP_E_STATE, "snapshot: every tree must be right after its initial update");
   }
-  if (!ctx->snap_hdr) HIP_TRY(ctx, hipMalloc(&ctx->snap_hdr, sizeof(TreeHdr) * B));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->snap_hdr, h.data(), sizeof(TreeHdr) * B, hipMemcpyHostToDevice,
-                              ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (!ctx->snap_hdr) PB_TRY(ctx, hipMalloc(&ctx->snap_hdr, sizeof(TreeHdr) * B));
+  if ((rc = ctx->upload(ctx->snap_hdr, h.data(), h.size())) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_snapshot = true;
   return POMCP_OK;
 }
@@ -1129,41 +1020,17 @@ int pomcp_snapshot(pomcp_ctx* ctx) {
 int pomcp_restore(pomcp_ctx* ctx) {
   if (!ctx) return POMCP_E_INVALID;
   if (!ctx->have_snapshot) return fail(ctx, POMCP_E_STATE, "restore without snapshot");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_restore, dim3(grid_blocks(ctx->dp.B)), dim3(256), 0, ctx->stream, ctx->dp,
                      ctx->snap_hdr);
-  HIP_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipGetLastError());
   ctx->defer_pending = false;   // back to the post-update roots: no records left
   return POMCP_OK;
 }
 
 // ------------------------------------------------------------ batched episodes
 
-#define PB_EP_LAUNCH(ctx, KERNEL, grid, ...)                                                    \
-  do {                                                                                           \
-    if ((ctx)->dp.env == POMCP_ENV_PURSUIT_EVASION)                                              \
-      hipLaunchKernelGGL(KERNEL<EpPursuitEvasion>, grid, dim3(kEpThreads), 0, (ctx)->stream,     \
-                         __VA_ARGS__);                                                           \
-    else                                                                                         \
-      hipLaunchKernelGGL(KERNEL<EpDriving>, grid, dim3(kEpThreads), 0, (ctx)->stream,            \
-                         __VA_ARGS__);                                                           \
-  } while (0)
-
 static unsigned episode_blocks(int B) { return (unsigned)((B + kEpThreads - 1) / kEpThreads); }
-
-// The query-state buffer of pomcp_belief_stats and its results (also allocated
-// by launch_belief_stats on its first use).
-static int ensure_belief_buffers(pomcp_ctx* ctx) {
-  if (ctx->bel_out) return POMCP_OK;
-  void* p = nullptr;
-  int rc = dev_alloc(ctx, &p, sizeof(pomcp_belief_counts) * (size_t)ctx->dp.B);
-  if (rc != POMCP_OK) return rc;
-  ctx->bel_out = reinterpret_cast<pomcp_belief_counts*>(p);
-  rc = dev_alloc(ctx, &p, sizeof(uint2) * (size_t)ctx->dp.B);
-  if (rc != POMCP_OK) return rc;
-  ctx->bel_q = reinterpret_cast<uint2*>(p);
-  return POMCP_OK;
-}
 
 int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
                          int32_t max_steps, int32_t until) {
@@ -1173,33 +1040,26 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     return fail(ctx, POMCP_E_INVALID, "episodes_begin: bad arguments");
   if (ctx->dp.tm && !ctx->tm_set)
     return fail(ctx, POMCP_E_STATE, "episodes_begin: pomcp_set_type_policies first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
   EpDev& ep = ctx->ep;
+  const size_t nB = (size_t)B;
   int rc;
-  void* q = nullptr;
   for (hipEvent_t& e : ctx->ep_ev)
-    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    if (!e) PB_TRY(ctx, hipEventCreate(&e));
   if (!ep.out) {   // (the last one allocated: a failed attempt is started over)
-    if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_episode_state) * (size_t)B)) != POMCP_OK) return rc;
-    ep.st = reinterpret_cast<pomcp_episode_state*>(q);
-    if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_root_stats) * (size_t)B)) != POMCP_OK) return rc;
-    ep.kept = reinterpret_cast<pomcp_root_stats*>(q);
-    if ((rc = dev_alloc(ctx, &q, sizeof(uint64_t) * (size_t)B)) != POMCP_OK) return rc;
-    ep.env_seeds = reinterpret_cast<const uint64_t*>(q);
-    if ((rc = dev_alloc(ctx, &q, sizeof(int32_t) * 2 * (size_t)episode_blocks(B))) != POMCP_OK)
+    if ((rc = ctx->alloc(ep.st, nB)) != POMCP_OK || (rc = ctx->alloc(ep.kept, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(ep.env_seeds, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(ep.part, 2 * (size_t)episode_blocks(B))) != POMCP_OK)
       return rc;
-    ep.part = reinterpret_cast<int32_t*>(q);
     ep.in_actions = const_cast<int32_t*>(ctx->dp.in_actions);
     ep.in_obs = const_cast<uint64_t*>(ctx->dp.in_obs);
-    if ((rc = dev_alloc(ctx, &q, sizeof(int32_t) * 2)) != POMCP_OK) return rc;
-    ep.out = reinterpret_cast<int32_t*>(q);
+    if ((rc = ctx->alloc(ep.out, 2)) != POMCP_OK) return rc;
   }
-  if (ep.pow_table == nullptr || ep.max_steps != max_steps) {
-    // (an earlier, shorter table stays allocated until the context goes)
-    if ((rc = dev_alloc(ctx, &q, sizeof(double) * (size_t)max_steps)) != POMCP_OK) return rc;
-    ep.pow_table = reinterpret_cast<const double*>(q);
-  }
+  // (an earlier, shorter table stays allocated until the context goes)
+  if ((ep.pow_table == nullptr || ep.max_steps != max_steps) &&
+      (rc = ctx->alloc(ep.pow_table, (size_t)max_steps)) != POMCP_OK)
+    return rc;
   ep.max_steps = max_steps;
   ep.until = until;
   ep.states = nullptr;
@@ -1207,20 +1067,13 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
     ep.states = ctx->bel_q;
   }
-  if (!ctx->ep_ps) {
-    if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_episode_pop_state) * (size_t)B)) != POMCP_OK)
-      return rc;
-    ctx->ep_ps = reinterpret_cast<pomcp_episode_pop_state*>(q);
-  }
+  if (!ctx->ep_ps && (rc = ctx->alloc(ctx->ep_ps, nB)) != POMCP_OK) return rc;
   ep.ps = ctx->ep_ps;
   ep.pop = nullptr;
   if (ctx->ep_pop_set) {
-    if (!ctx->dev_pop) {
-      if ((rc = dev_alloc(ctx, &q, sizeof(EpPopTables))) != POMCP_OK) return rc;
-      ctx->dev_pop = reinterpret_cast<EpPopTables*>(q);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dev_pop, &ctx->host_pop, sizeof(EpPopTables),
-                                hipMemcpyHostToDevice, ctx->stream));
+    if ((!ctx->dev_pop && (rc = ctx->alloc(ctx->dev_pop, 1)) != POMCP_OK) ||
+        (rc = ctx->upload(ctx->dev_pop, &ctx->host_pop, 1)) != POMCP_OK)
+      return rc;
     ep.pop = ctx->dev_pop;
   }
   ep.acc_part = nullptr;
@@ -1231,21 +1084,16 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
     ep.states = ctx->bel_q;
     const int nparts = B < kBelMaxGrid ? B : kBelMaxGrid;
-    if (!acc.part) {   // (the last one allocated)
-      if ((rc = dev_alloc(ctx, &q, sizeof(pomcp_episode_belief_acc) * (size_t)B)) != POMCP_OK)
-        return rc;
-      acc.rec = reinterpret_cast<pomcp_episode_belief_acc*>(q);
-      if ((rc = dev_alloc(ctx, &q, sizeof(ctx->host_other_pi))) != POMCP_OK) return rc;
-      acc.other_pi = reinterpret_cast<const double*>(q);
-      if ((rc = dev_alloc(ctx, &q, sizeof(int32_t) * (size_t)nparts)) != POMCP_OK) return rc;
-      acc.part = reinterpret_cast<int32_t*>(q);
-    }
+    constexpr size_t kPi = sizeof(ctx->host_other_pi) / sizeof(double);
+    if (!acc.part &&   // (the last one allocated)
+        ((rc = ctx->alloc(acc.rec, nB)) != POMCP_OK || (rc = ctx->alloc(acc.other_pi, kPi)) != POMCP_OK ||
+         (rc = ctx->alloc(acc.part, (size_t)nparts)) != POMCP_OK))
+      return rc;
     const int64_t want = ctx->ep_acc_steps_want ? (int64_t)B * max_steps * 3 : 0;
     if (want > ctx->acc_steps_cap) {
       // (an earlier, smaller table stays allocated until the context goes)
-      if ((rc = dev_alloc(ctx, &q, sizeof(double) * (size_t)want)) != POMCP_OK) return rc;
+      if ((rc = ctx->alloc(ctx->acc_steps_buf, (size_t)want)) != POMCP_OK) return rc;
       ctx->acc_steps_cap = want;
-      ctx->acc_steps_buf = reinterpret_cast<double*>(q);
     }
     acc.steps = ctx->ep_acc_steps_want ? ctx->acc_steps_buf : nullptr;
     acc.st = ep.st;
@@ -1254,26 +1102,25 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     // particles carry a policy on a type-based context that draws one per particle
     acc.num_other = ctx->dp.tm && !ctx->host_tm.no_mixture_draw ? ctx->host_tm.n_other : 0;
     acc.max_steps = max_steps;
-    HIP_TRY(ctx, hipMemcpyAsync(const_cast<double*>(acc.other_pi), ctx->host_other_pi,
-                                sizeof(ctx->host_other_pi), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(acc.rec, 0, sizeof(pomcp_episode_belief_acc) * (size_t)B,
-                                ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(acc.part, 0, sizeof(int32_t) * (size_t)nparts, ctx->stream));
+    if ((rc = ctx->upload(acc.other_pi, &ctx->host_other_pi[0][0], kPi)) != POMCP_OK) return rc;
+    PB_TRY(ctx, hipMemsetAsync(acc.rec, 0, sizeof(pomcp_episode_belief_acc) * nB, ctx->stream));
+    PB_TRY(ctx, hipMemsetAsync(acc.part, 0, sizeof(int32_t) * (size_t)nparts, ctx->stream));
     ep.acc_part = acc.part;
     ep.acc_nparts = nparts;
   }
   ctx->ep_active = false;
   if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint64_t*>(ep.env_seeds), env_seeds,
-                              sizeof(uint64_t) * (size_t)B, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(const_cast<double*>(ep.pow_table), pow_table,
-                              sizeof(double) * (size_t)max_steps, hipMemcpyHostToDevice,
-                              ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(ep.kept, 0, sizeof(pomcp_root_stats) * (size_t)B, ctx->stream));
-  PB_EP_LAUNCH(ctx, k_episode_reset, dim3(episode_blocks(B)), ctx->dp, ep);
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = ctx->upload(ep.env_seeds, env_seeds, nB)) != POMCP_OK ||
+      (rc = ctx->upload(ep.pow_table, pow_table, (size_t)max_steps)) != POMCP_OK)
+    return rc;
+  PB_TRY(ctx, hipMemsetAsync(ep.kept, 0, sizeof(pomcp_root_stats) * nB, ctx->stream));
+  with_episode_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_episode_reset<decltype(e)>, dim3(episode_blocks(B)), dim3(kEpThreads), 0,
+                       ctx->stream, ctx->dp, ep);
+  });
+  PB_TRY(ctx, hipGetLastError());
   // the tables were copied from the caller's memory: finish before returning
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->ep_active = true;
   ctx->ep_steps = 0;
   ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
@@ -1286,72 +1133,69 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
   if (!ctx) return POMCP_E_INVALID;
   if (num_sims < 0 || !live_out) return fail(ctx, POMCP_E_INVALID, "episodes_step: bad arguments");
   if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_step: pomcp_episodes_begin first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
   const bool reroot = ctx->ep_steps > 0;   // not the batch's first step
-  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[0], ctx->stream));
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[0], ctx->stream));
   int rc = launch_update(ctx, reroot);
   if (rc != POMCP_OK) return rc;
   ctx->defer_pending = false;   // k_compact_log materialised the surviving deferred children
   ctx->have_root = true;
-  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[1], ctx->stream));
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[1], ctx->stream));
   if ((rc = launch_search(ctx, num_sims, 1)) != POMCP_OK) return rc;
-  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[2], ctx->stream));
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[2], ctx->stream));
   const unsigned nblk = episode_blocks(B);
-  PB_EP_LAUNCH(ctx, k_episode_step, dim3(nblk), ctx->dp, ctx->ep);
-  HIP_TRY(ctx, hipGetLastError());
+  with_episode_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_episode_step<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
+                       ctx->dp, ctx->ep);
+  });
+  PB_TRY(ctx, hipGetLastError());
   if (ctx->ep_acc) {
     // the accuracies of the trees that played, against what k_episode_step wrote
-    HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[4], ctx->stream));
+    PB_TRY(ctx, hipEventRecord(ctx->ep_ev[4], ctx->stream));
     hipLaunchKernelGGL(k_episode_belief_acc, dim3((unsigned)ctx->ep.acc_nparts), dim3(kBelThreads),
                        0, ctx->stream, ctx->dp, ctx->acc);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[5], ctx->stream));
+    PB_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipEventRecord(ctx->ep_ev[5], ctx->stream));
   }
   hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
+  PB_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
   int32_t counts[2] = {0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
-                              ctx->stream));
+  PB_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
+                             ctx->stream));
   uint32_t lf_fail = 0u;
   if (reroot && !ctx->log_scan_legacy)
-    HIP_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                                ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    PB_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               ctx->stream));
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->ep_steps += 1;
   for (int k = 0; k < 3; ++k) {
     float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
+    PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
     ctx->ep_ms[k] += (double)ms;
   }
   if (ctx->ep_acc) {   // its own figure, not a part of slot 2
     float ms = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[4], ctx->ep_ev[5]));
+    PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[4], ctx->ep_ev[5]));
     ctx->ep_acc_ms += (double)ms;
     ctx->ep_ms[2] -= (double)ms;
   }
   if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
   *live_out = counts[0];
   if (counts[1] != 0) {   // some tree failed: the update's error first, then the search's
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_upd.data(), ctx->dp.upd_out, sizeof(int32_t) * 2 * B,
-                                hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    rc = first_tree_error(ctx, ctx->host_upd.data(), 2, 1, "update");
-    if (rc != POMCP_OK) return rc;
-    rc = pomcp_get_root_stats(ctx, ctx->host_stats.data());
-    if (rc != POMCP_OK) return rc;
+    if ((rc = ctx->fetch(ctx->host_upd.data(), ctx->dp.upd_out, 2 * (size_t)B)) != POMCP_OK ||
+        (rc = first_update_error(ctx)) != POMCP_OK ||
+        (rc = pomcp_get_root_stats(ctx, ctx->host_stats.data())) != POMCP_OK)
+      return rc;
     if (ctx->ep_acc) {
       std::vector<pomcp_episode_belief_acc> rec((size_t)B);
-      HIP_TRY(ctx, hipMemcpyAsync(rec.data(), ctx->acc.rec, sizeof(rec[0]) * (size_t)B,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      for (int t = 0; t < B; ++t)
-        if (rec[t].error != 0)
-          return fail(ctx, rec[t].error, "episodes_step: belief accuracy of tree " +
-                                             std::to_string(t) + ": error " +
-                                             std::to_string(rec[t].error) +
-                                             " (its own, or a particle's policy index out of range)");
+      if ((rc = ctx->fetch(rec.data(), ctx->acc.rec, rec.size())) != POMCP_OK) return rc;
+      rc = first_error(ctx, B, [&](int t) { return rec[t].error; }, [](int t, int e) {
+        return "episodes_step: belief accuracy of tree " + std::to_string(t) + ": error " +
+               std::to_string(e) + " (its own, or a particle's policy index out of range)";
+      });
+      if (rc != POMCP_OK) return rc;
     }
     return fail(ctx, POMCP_E_STATE, "episodes_step: an episode record reports an error");
   }
@@ -1361,11 +1205,8 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
 int pomcp_episodes_states(pomcp_ctx* ctx, pomcp_episode_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
   if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_states: pomcp_episodes_begin first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->ep.st, sizeof(pomcp_episode_state) * (size_t)ctx->dp.B,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, ctx->ep.st, (size_t)ctx->dp.B);
 }
 
 int pomcp_episodes_results(pomcp_ctx* ctx, pomcp_episode_result* out) {
@@ -1390,19 +1231,14 @@ int pomcp_episodes_belief_stats(pomcp_ctx* ctx, pomcp_belief_counts* out) {
                                     "pomcp_episodes_begin");
   int rc = belief_stats_ready(ctx);
   if (rc != POMCP_OK) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   // the query states are on the device already (k_episode_reset / k_episode_step)
   rc = launch_belief_stats(ctx, reinterpret_cast<const uint32_t*>(ctx->bel_q), false);
   if (rc != POMCP_OK) return rc;
-  const int B = ctx->dp.B;
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->bel_out, sizeof(pomcp_belief_counts) * (size_t)B,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  for (int t = 0; t < B; ++t)
-    if (out[t].error != 0)
-      return fail(ctx, out[t].error, "episodes_belief_stats: tree " + std::to_string(t) +
-                                         ": error " + std::to_string(out[t].error));
-  return POMCP_OK;
+  if ((rc = ctx->fetch(out, ctx->bel_out, (size_t)ctx->dp.B)) != POMCP_OK) return rc;
+  return first_error(ctx, ctx->dp.B, [&](int t) { return out[t].error; }, [](int t, int e) {
+    return "episodes_belief_stats: tree " + std::to_string(t) + ": error " + std::to_string(e);
+  });
 }
 
 int pomcp_episodes_set_population(pomcp_ctx* ctx, const pomcp_episode_population* pop) {
@@ -1427,11 +1263,8 @@ int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
   if (!ctx->ep_active)
     return fail(ctx, POMCP_E_STATE, "episodes_pop_states: pomcp_episodes_begin first");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->ep_ps, sizeof(pomcp_episode_pop_state) * (size_t)ctx->dp.B,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, ctx->ep_ps, (size_t)ctx->dp.B);
 }
 
 int pomcp_episodes_track_belief_acc(pomcp_ctx* ctx, int32_t on, int32_t per_step) {
@@ -1446,12 +1279,8 @@ int pomcp_episodes_belief_acc(pomcp_ctx* ctx, pomcp_episode_belief_acc* out) {
   if (!ctx->ep_active || !ctx->ep_acc)
     return fail(ctx, POMCP_E_STATE, "episodes_belief_acc: pomcp_episodes_track_belief_acc(1, ..), "
                                     "then pomcp_episodes_begin");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->acc.rec,
-                              sizeof(pomcp_episode_belief_acc) * (size_t)ctx->dp.B,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, ctx->acc.rec, (size_t)ctx->dp.B);
 }
 
 int pomcp_episodes_belief_acc_steps(pomcp_ctx* ctx, double* out) {
@@ -1459,12 +1288,8 @@ int pomcp_episodes_belief_acc_steps(pomcp_ctx* ctx, double* out) {
   if (!ctx->ep_active || !ctx->ep_acc || ctx->acc.steps == nullptr)
     return fail(ctx, POMCP_E_STATE, "episodes_belief_acc_steps: pomcp_episodes_track_belief_acc("
                                     "1, 1), then pomcp_episodes_begin");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->acc.steps,
-                              sizeof(double) * 3 * (size_t)ctx->dp.B * (size_t)ctx->acc.max_steps,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, ctx->acc.steps, 3 * (size_t)ctx->dp.B * (size_t)ctx->acc.max_steps);
 }
 
 int pomcp_episodes_belief_acc_ms(pomcp_ctx* ctx, double* ms) {
@@ -1542,11 +1367,11 @@ int pomcp_debug_belief_stats_ms(pomcp_ctx* ctx, const uint32_t* states, int32_t 
   if (!ctx || !ms_per_launch || reps < 1) return POMCP_E_INVALID;
   int rc = belief_stats_ready(ctx);
   if (rc != POMCP_OK) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
   rc = launch_belief_stats(ctx, states);
   if (rc != POMCP_OK) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_TRY(ctx, hipEventCreate(&e0));
+  PB_TRY(ctx, hipEventCreate(&e0));
   hipError_t e = hipEventCreate(&e1);
   if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
   for (int32_t r = 0; r < reps && e == hipSuccess; ++r) {
@@ -1599,18 +1424,16 @@ int pomcp_debug_phase_timing(pomcp_ctx* ctx, uint64_t* out, int32_t capacity, in
 #else
   const int64_t waves = search_waves(ctx->dp.B);
   if (ctx->dp.timing == nullptr) {   // first call: allocate; the next search fills it
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, sizeof(uint64_t) * 16 * (size_t)waves) != POMCP_OK) return POMCP_E_HIP;
-    HIP_TRY(ctx, hipMemset(p, 0, sizeof(uint64_t) * 16 * (size_t)waves));
-    ctx->dp.timing = reinterpret_cast<uint64_t*>(p);
+    if (ctx->alloc(ctx->dp.timing, 16 * (size_t)waves) != POMCP_OK) return POMCP_E_HIP;
+    PB_TRY(ctx, hipMemset(ctx->dp.timing, 0, sizeof(uint64_t) * 16 * (size_t)waves));
     *count = 0;
     return POMCP_OK;
   }
   *count = (int32_t)(16 * waves);
   if (out && capacity >= *count) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(out, ctx->dp.timing, sizeof(uint64_t) * 16 * (size_t)waves,
-                           hipMemcpyDeviceToHost));
+    PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    PB_TRY(ctx, hipMemcpy(out, ctx->dp.timing, sizeof(uint64_t) * 16 * (size_t)waves,
+                          hipMemcpyDeviceToHost));
   }
   return POMCP_OK;
 #endif

@@ -174,7 +174,110 @@ def log_table(n: int) -> np.ndarray:
     return _LOG_TABLE[:n]
 
 
-class PomcpEngine:
+class EngineBase:
+    """What the handles on a ``pomcp_ctx`` (``PomcpEngine``) and an ``intmcp_ctx``
+    (``IntmcpEngine``) share: the step limit, the base ``pomcp_config`` and the
+    calls both C ABIs have under their own prefix.  A subclass sets ``model``,
+    ``config``, ``ego``, ``A`` and its batch size ``_B`` first."""
+
+    ABI = "pomcp"   # prefix of the C symbols: <ABI>_destroy, <ABI>_last_error, <ABI>_update, ...
+
+    def _resolve_step_limit(self):
+        if self.config.step_limit is not None:
+            self.step_limit = int(self.config.step_limit)
+        elif getattr(self.model, "spec", None) is not None and self.model.spec.max_episode_steps:
+            self.step_limit = int(self.model.spec.max_episode_steps)
+        else:
+            self.step_limit = INT32_MAX
+        return self.step_limit
+
+    def _search_budget(self, searches):
+        """Searches the arenas are planned for: the caller's, or an episode's."""
+        if searches is not None:
+            return searches
+        return (self.step_limit if self.step_limit < INT32_MAX else 100) + 1
+
+    def _fill_config(self, c, capacities, seed, tree_key_base):
+        """The fields of a ``pomcp_config`` every engine sets; keeps its tables alive."""
+        config = self.config
+        c.abi_version = N.POMCP_ABI_VERSION
+        c.num_agents = len(self.model.possible_agents)
+        c.ego_agent = self.ego
+        c.num_actions = self.A
+        c.action_selection = self.SELECTION[config.action_selection]
+        c.depth_limit = min(config.depth_limit, INT32_MAX)
+        c.step_limit = self.step_limit
+        c.num_particles = config.num_particles
+        c.extra_particles = config.extra_particles
+        kb = config.known_bounds
+        c.has_known_bounds = 1 if kb else 0
+        if kb:
+            c.known_min, c.known_max = float(kb[0]), float(kb[1])
+        c.num_trees = self._B
+        c.discount = config.discount
+        c.c = config.c
+        c.pucb_exploration_fraction = config.pucb_exploration_fraction
+        c.reinvigoration_sample_limit_factor = config.reinvigoration_sample_limit_factor
+        s = config.seed if seed is None else seed
+        if s is None:
+            s = int(np.random.SeedSequence().entropy) & (2**63 - 1)
+        c.seed = int(s) & (2**64 - 1)
+        c.tree_key_base = int(tree_key_base)
+        # FP64 tables from Python's own math.log and float ** int (bit-exact with
+        # mcts.py:534 and mcts.py:421)
+        self._logtab = log_table(capacities.log_table_size)
+        self._dpow = np.array([config.discount ** k for k in range(capacities.discount_pow_size)],
+                              dtype=np.float64)
+        c.log_table = self._logtab.ctypes.data_as(C.POINTER(C.c_double))
+        c.log_table_size = len(self._logtab)
+        c.discount_pow = self._dpow.ctypes.data_as(C.POINTER(C.c_double))
+        c.discount_pow_size = len(self._dpow)
+        self.model.configure_engine(c)
+
+    def _fn(self, name):
+        return getattr(self._lib, f"{self.ABI}_{name}")
+
+    def close(self):
+        if getattr(self, "_ctx", None):
+            self._fn("destroy")(self._ctx)
+            self._ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        N.check(rc, self._ctx, what, last_error=self.ABI + "_last_error")
+
+    def reset(self):
+        self._check(self._fn("reset")(self._ctx), "reset")
+
+    def update(self, actions, obs_keys):
+        B = self._B
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.int32), (B,)))
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(obs_keys, dtype=np.uint64), (B,)))
+        absorbing = np.zeros(B, dtype=np.int32)
+        self._check(self._fn("update")(
+            self._ctx, a.ctypes.data_as(C.POINTER(C.c_int32)),
+            o.ctypes.data_as(C.POINTER(C.c_uint64)),
+            absorbing.ctypes.data_as(C.POINTER(C.c_int32))), "update")
+        return absorbing.astype(bool)
+
+    def root_stats(self):
+        self._check(self._fn("get_root_stats")(self._ctx, self._stats), "get_root_stats")
+        return self._stats
+
+    def synthetic_obs(self, env_seed_base):
+        out = np.zeros(self._B, dtype=np.uint64)
+        self._check(self._fn("synthetic_obs")(
+            self._ctx, int(env_seed_base), out.ctypes.data_as(C.POINTER(C.c_uint64))),
+            "synthetic_obs")
+        return out
+
+
+class PomcpEngine(EngineBase):
     SELECTION = {"pucb": N.SEL_PUCB, "ucb": N.SEL_UCB, "uniform": N.SEL_UNIFORM}
 
     def __init__(self, model, agent_id, config, num_trees=1, capacities=None, num_sims=None,
@@ -187,65 +290,25 @@ class PomcpEngine:
             raise NotImplementedError("truncated search needs a value function (none on GPU)")
         self.model = model
         self.config = config
-        self.num_trees = int(num_trees)
+        self.num_trees = self._B = int(num_trees)
         self.ego = model.possible_agents.index(agent_id)
         self.A = model.action_spaces[agent_id].n
-        if config.step_limit is not None:
-            step_limit = int(config.step_limit)
-        elif getattr(model, "spec", None) is not None and model.spec.max_episode_steps:
-            step_limit = int(model.spec.max_episode_steps)
-        else:
-            step_limit = INT32_MAX
-        self.step_limit = step_limit
+        step_limit = self._resolve_step_limit()
         self.wall_clock_sims = None
         if capacities is None and wall_clock:
             capacities, self.wall_clock_sims = plan_wallclock_capacities(
                 config, step_limit, self.num_trees, model.action_spaces[agent_id].n)
         if capacities is None:
             sims = num_sims if num_sims is not None else (config.num_sims or 4096)
-            budget = searches if searches is not None else (
-                (step_limit if step_limit < INT32_MAX else 100) + 1)
-            capacities = plan_capacities(config, step_limit, sims, budget,
+            capacities = plan_capacities(config, step_limit, sims, self._search_budget(searches),
                                          num_actions=self.A)
         self.capacities = capacities
         c = N.PomcpConfig()
-        c.abi_version = N.POMCP_ABI_VERSION
-        c.num_agents = len(model.possible_agents)
-        c.ego_agent = self.ego
-        c.num_actions = self.A
-        c.action_selection = self.SELECTION[config.action_selection]
-        c.depth_limit = min(config.depth_limit, INT32_MAX)
-        c.step_limit = step_limit
-        c.num_particles = config.num_particles
-        c.extra_particles = config.extra_particles
-        kb = config.known_bounds
-        c.has_known_bounds = 1 if kb else 0
-        if kb:
-            c.known_min, c.known_max = float(kb[0]), float(kb[1])
-        c.num_trees = self.num_trees
-        c.discount = config.discount
-        c.c = config.c
-        c.pucb_exploration_fraction = config.pucb_exploration_fraction
-        c.reinvigoration_sample_limit_factor = config.reinvigoration_sample_limit_factor
-        s = config.seed if seed is None else seed
-        if s is None:
-            s = int(np.random.SeedSequence().entropy) & (2**63 - 1)
-        c.seed = int(s) & (2**64 - 1)
-        c.tree_key_base = int(tree_key_base)
+        self._fill_config(c, capacities, seed, tree_key_base)
         c.max_blocks = capacities.max_blocks
         c.max_particles = capacities.max_particles
         c.max_belief = capacities.max_belief
         c.overflow_slots = capacities.overflow_slots
-        # FP64 tables from Python's own math.log and float ** int (bit-exact with
-        # mcts.py:534 and mcts.py:421)
-        self._logtab = log_table(capacities.log_table_size)
-        self._dpow = np.array([config.discount ** k for k in range(capacities.discount_pow_size)],
-                              dtype=np.float64)
-        c.log_table = self._logtab.ctypes.data_as(C.POINTER(C.c_double))
-        c.log_table_size = len(self._logtab)
-        c.discount_pow = self._dpow.ctypes.data_as(C.POINTER(C.c_double))
-        c.discount_pow_size = len(self._dpow)
-        model.configure_engine(c)
         c.type_based = 1 if type_policies is not None else 0
         self.type_based = type_policies is not None
         self._cfg = c
@@ -272,22 +335,12 @@ class PomcpEngine:
             self._defer_forced = True
 
     # ------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_ctx", None):
-            self._lib.pomcp_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        N.check(rc, self._ctx, what)
-
-    def reset(self):
-        self._check(self._lib.pomcp_reset(self._ctx), "reset")
+    def _tree_records(self, name, dtype, ctype, *args):
+        """A structured array of ``dtype`` for every tree, filled by the C
+        function ``pomcp_<name>(ctx, *args, out)``."""
+        out = np.zeros(self.num_trees, dtype=dtype)
+        self._check(self._fn(name)(self._ctx, *args, out.ctypes.data_as(C.POINTER(ctype))), name)
+        return out
 
     def root_prior(self, tree=0):
         """Type-based: the root's ObsNode.action_probs (num_actions doubles)."""
@@ -305,17 +358,6 @@ class PomcpEngine:
             self._ctx, int(tree), out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
             "get_root_policies")
         return out[:n.value]
-
-    def update(self, actions, obs_keys):
-        B = self.num_trees
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.int32), (B,)))
-        o = np.ascontiguousarray(np.broadcast_to(np.asarray(obs_keys, dtype=np.uint64), (B,)))
-        absorbing = np.zeros(B, dtype=np.int32)
-        self._check(self._lib.pomcp_update(
-            self._ctx, a.ctypes.data_as(C.POINTER(C.c_int32)),
-            o.ctypes.data_as(C.POINTER(C.c_uint64)),
-            absorbing.ctypes.data_as(C.POINTER(C.c_int32))), "update")
-        return absorbing.astype(bool)
 
     def search(self, num_sims, fetch=True, final=True):
         """``num_sims`` simulations per tree; ``final=False`` leaves out the final
@@ -358,10 +400,6 @@ class PomcpEngine:
         (``pomcp_debug_search_depth_spec``): 1..3, or 0 for the generic kernel."""
         return int(self._lib.pomcp_debug_search_depth_spec(self._ctx))
 
-    def root_stats(self):
-        self._check(self._lib.pomcp_get_root_stats(self._ctx, self._stats), "get_root_stats")
-        return self._stats
-
     def root_belief(self, tree=0):
         n = C.c_int32()
         self._check(self._lib.pomcp_get_root_belief(self._ctx, tree, None, 0, C.byref(n)),
@@ -379,15 +417,12 @@ class PomcpEngine:
         ``state_matches`` against ``states`` ((v0, v1) per tree, or one pair for
         every tree; -1 without), ``policy_hist`` (type-based engines) and
         ``error``.  Raises if a tree reports an error."""
-        out = np.zeros(self.num_trees, dtype=N.BELIEF_COUNTS_DTYPE)
         q = None
         if states is not None:
             s = np.ascontiguousarray(np.broadcast_to(
                 np.asarray(states, dtype=np.uint32).reshape(-1, 2), (self.num_trees, 2)))
             q = s.ctypes.data_as(C.POINTER(C.c_uint32))
-        self._check(self._lib.pomcp_belief_stats(
-            self._ctx, q, out.ctypes.data_as(C.POINTER(N.PomcpBeliefCounts))), "belief_stats")
-        return out
+        return self._tree_records("belief_stats", N.BELIEF_COUNTS_DTYPE, N.PomcpBeliefCounts, q)
 
     def set_root_belief(self, tree, rows):
         """Root belief of a fresh tree from host particles ((t, v0, v1) rows)."""
@@ -438,13 +473,6 @@ class PomcpEngine:
                     "merge_roots")
         return out
 
-    def synthetic_obs(self, env_seed_base):
-        out = np.zeros(self.num_trees, dtype=np.uint64)
-        self._check(self._lib.pomcp_synthetic_obs(
-            self._ctx, int(env_seed_base), out.ctypes.data_as(C.POINTER(C.c_uint64))),
-            "synthetic_obs")
-        return out
-
     def synthetic_step(self, env_seed_base, actions):
         """The synthetic roots' environment answer to ``actions`` (bench): the
         ego's next observation key per tree (``pomcp_synthetic_step``)."""
@@ -481,25 +509,17 @@ class PomcpEngine:
 
     def episodes_results(self):
         """Every tree's ``pomcp_episode_result`` as a structured array."""
-        out = np.zeros(self.num_trees, dtype=N.EPISODE_RESULT_DTYPE)
-        self._check(self._lib.pomcp_episodes_results(
-            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeResult))), "episodes_results")
-        return out
+        return self._tree_records("episodes_results", N.EPISODE_RESULT_DTYPE, N.PomcpEpisodeResult)
 
     def episodes_states(self):
         """Every tree's whole ``pomcp_episode_state`` (tests and diagnostics)."""
-        out = np.zeros(self.num_trees, dtype=N.EPISODE_STATE_DTYPE)
-        self._check(self._lib.pomcp_episodes_states(
-            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeState))), "episodes_states")
-        return out
+        return self._tree_records("episodes_states", N.EPISODE_STATE_DTYPE, N.PomcpEpisodeState)
 
     def episodes_belief_counts(self):
         """``belief_counts`` against the true states the episode kernels wrote on
         the device (``episodes_begin(..., track_states=True)``)."""
-        out = np.zeros(self.num_trees, dtype=N.BELIEF_COUNTS_DTYPE)
-        self._check(self._lib.pomcp_episodes_belief_stats(
-            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpBeliefCounts))), "episodes_belief_stats")
-        return out
+        return self._tree_records("episodes_belief_stats", N.BELIEF_COUNTS_DTYPE,
+                                  N.PomcpBeliefCounts)
 
     def episodes_set_population(self, probs=None, mixture_index=None):
         """The other agents' population of the batches started from now on
@@ -531,10 +551,8 @@ class PomcpEngine:
     def episodes_pop_states(self):
         """Every tree's ``pomcp_episode_pop_state``: the policy index its episode
         drew from the population (-1 without one) and that policy's mixture index."""
-        out = np.zeros(self.num_trees, dtype=N.EPISODE_POP_STATE_DTYPE)
-        self._check(self._lib.pomcp_episodes_pop_states(
-            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodePopState))), "episodes_pop_states")
-        return out
+        return self._tree_records("episodes_pop_states", N.EPISODE_POP_STATE_DTYPE,
+                                  N.PomcpEpisodePopState)
 
     def episodes_track_belief_acc(self, on, per_step=False):
         """Accumulate the belief accuracies of every played step on the device
@@ -545,10 +563,8 @@ class PomcpEngine:
     def episodes_belief_acc(self):
         """Every tree's ``pomcp_episode_belief_acc``: the sequential FP64 sums of
         its steps' state / policy / action accuracies, their count, its error."""
-        out = np.zeros(self.num_trees, dtype=N.EPISODE_BELIEF_ACC_DTYPE)
-        self._check(self._lib.pomcp_episodes_belief_acc(
-            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeBeliefAcc))), "episodes_belief_acc")
-        return out
+        return self._tree_records("episodes_belief_acc", N.EPISODE_BELIEF_ACC_DTYPE,
+                                  N.PomcpEpisodeBeliefAcc)
 
     def episodes_belief_acc_steps(self, max_steps):
         """The per-step table [num_trees][max_steps][3] (state, policy, action);

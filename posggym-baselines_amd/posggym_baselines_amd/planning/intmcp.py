@@ -45,7 +45,7 @@ from posggym_baselines_amd.envs import engine_model
 
 from posggym_baselines_amd import _native as N
 from posggym_baselines_amd.planning.config import MCTSConfig
-from posggym_baselines_amd.planning.engine import log_table
+from posggym_baselines_amd.planning.engine import EngineBase
 from posggym_baselines_amd.planning.search_policy import RandomSearchPolicy
 from posggym_baselines_amd.planning.utils import PlanningStatTracker
 
@@ -152,9 +152,10 @@ def plan_intmcp_wallclock_capacities(config, step_limit: int, num_actions: int,
     return caps, sims
 
 
-class IntmcpEngine:
+class IntmcpEngine(EngineBase):
     """Python handle on one ``intmcp_ctx`` (``num_pairs`` planner pairs)."""
 
+    ABI = "intmcp"
     SELECTION = {"ucb": N.SEL_UCB, "uniform": N.SEL_UNIFORM}
 
     def __init__(self, model, agent_id, config, num_pairs=1, capacities=None, num_sims=None,
@@ -171,7 +172,7 @@ class IntmcpEngine:
         self.model = model
         self._emodel = engine_model(model)
         self.config = config
-        self.num_pairs = int(num_pairs)
+        self.num_pairs = self._B = int(num_pairs)
         if not 0 <= int(nesting_level) <= MAX_NESTING:
             raise NotImplementedError(f"the GPU I-NTMCP engine runs nesting levels 0 to {MAX_NESTING}")
         self.nesting_level = int(nesting_level)
@@ -180,57 +181,19 @@ class IntmcpEngine:
         other = model.possible_agents[1 - self.ego]
         if model.action_spaces[other].n != self.A:
             raise NotImplementedError("both agents need the same action count")
-        if config.step_limit is not None:
-            step_limit = int(config.step_limit)
-        elif getattr(model, "spec", None) is not None and model.spec.max_episode_steps:
-            step_limit = int(model.spec.max_episode_steps)
-        else:
-            step_limit = INT32_MAX
-        self.step_limit = step_limit
+        step_limit = self._resolve_step_limit()
         self.wall_clock_sims = None
         if capacities is None and wall_clock:
             capacities, self.wall_clock_sims = plan_intmcp_wallclock_capacities(
                 config, step_limit, self.A, self.nesting_level)
         if capacities is None:
             sims = num_sims if num_sims is not None else (config.num_sims or 1024)
-            budget = searches if searches is not None else (
-                (step_limit if step_limit < INT32_MAX else 100) + 1)
-            capacities = plan_intmcp_capacities(config, step_limit, sims, budget, self.A,
+            capacities = plan_intmcp_capacities(config, step_limit, sims,
+                                                self._search_budget(searches), self.A,
                                                 self.nesting_level)
         self.capacities = capacities
         ic = N.IntmcpConfig()
-        c = ic.base
-        c.abi_version = N.POMCP_ABI_VERSION
-        c.num_agents = 2
-        c.ego_agent = self.ego
-        c.num_actions = self.A
-        c.action_selection = self.SELECTION[config.action_selection]
-        c.depth_limit = min(config.depth_limit, INT32_MAX)
-        c.step_limit = step_limit
-        c.num_particles = config.num_particles
-        c.extra_particles = config.extra_particles
-        kb = config.known_bounds
-        c.has_known_bounds = 1 if kb else 0
-        if kb:
-            c.known_min, c.known_max = float(kb[0]), float(kb[1])
-        c.num_trees = self.num_pairs
-        c.discount = config.discount
-        c.c = config.c
-        c.pucb_exploration_fraction = config.pucb_exploration_fraction
-        c.reinvigoration_sample_limit_factor = config.reinvigoration_sample_limit_factor
-        s = config.seed if seed is None else seed
-        if s is None:
-            s = int(np.random.SeedSequence().entropy) & (2**63 - 1)
-        c.seed = int(s) & (2**64 - 1)
-        c.tree_key_base = int(tree_key_base)
-        self._logtab = log_table(capacities.log_table_size)
-        self._dpow = np.array([config.discount ** k for k in range(capacities.discount_pow_size)],
-                              dtype=np.float64)
-        c.log_table = self._logtab.ctypes.data_as(C.POINTER(C.c_double))
-        c.log_table_size = len(self._logtab)
-        c.discount_pow = self._dpow.ctypes.data_as(C.POINTER(C.c_double))
-        c.discount_pow_size = len(self._dpow)
-        model.configure_engine(c)
+        self._fill_config(ic.base, capacities, seed, tree_key_base)
         ic.state_belief_only = 1 if config.state_belief_only else 0
         ic.nesting_level = self.nesting_level
         ic.max_nodes = capacities.max_nodes
@@ -250,34 +213,6 @@ class IntmcpEngine:
         self._ctx = ctx
         self._lib = lib
         self._stats = (N.IntmcpRootStats * self.num_pairs)()
-
-    def close(self):
-        if getattr(self, "_ctx", None):
-            self._lib.intmcp_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        N.check(rc, self._ctx, what, last_error="intmcp_last_error")
-
-    def reset(self):
-        self._check(self._lib.intmcp_reset(self._ctx), "reset")
-
-    def update(self, actions, obs_keys):
-        B = self.num_pairs
-        a = np.ascontiguousarray(np.broadcast_to(np.asarray(actions, dtype=np.int32), (B,)))
-        o = np.ascontiguousarray(np.broadcast_to(np.asarray(obs_keys, dtype=np.uint64), (B,)))
-        absorbing = np.zeros(B, dtype=np.int32)
-        self._check(self._lib.intmcp_update(
-            self._ctx, a.ctypes.data_as(C.POINTER(C.c_int32)),
-            o.ctypes.data_as(C.POINTER(C.c_uint64)),
-            absorbing.ctypes.data_as(C.POINTER(C.c_int32))), "update")
-        return absorbing.astype(bool)
 
     def search(self, num_sims, fetch=True):
         if not fetch:
@@ -323,10 +258,6 @@ class IntmcpEngine:
         self._check(self._lib.intmcp_search_levels(self._ctx, int(level0_sims), int(level1_sims),
                                                    int(flags), ptr), "search_levels")
         return out
-
-    def root_stats(self):
-        self._check(self._lib.intmcp_get_root_stats(self._ctx, self._stats), "get_root_stats")
-        return self._stats
 
     def headroom(self, stats=None):
         """Simulations (of either level) that can still run in every pair
@@ -416,13 +347,6 @@ class IntmcpEngine:
             parts.ctypes.data_as(C.POINTER(C.c_uint32)), npart.value, C.byref(npart)),
             "get_support")
         return ent[:ne.value], parts[:2 * npart.value].reshape(-1, 2)
-
-    def synthetic_obs(self, env_seed_base):
-        out = np.zeros(self.num_pairs, dtype=np.uint64)
-        self._check(self._lib.intmcp_synthetic_obs(
-            self._ctx, int(env_seed_base), out.ctypes.data_as(C.POINTER(C.c_uint64))),
-            "synthetic_obs")
-        return out
 
 
 def node_order(info: int):

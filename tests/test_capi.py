@@ -194,3 +194,105 @@ def test_episode_loop_replays_golden_trajectories_on_cpu():
             assert [s[1] for s in seen] == [s["reward"] for s in steps], case
             assert rows[0]["len"] == ep["trace"]["len"]
             assert fhex(rows[0]["return"]) == ep["trace"]["return"]
+
+
+# ------------------------------------------------ create: configuration errors
+# Both create functions validate the configuration before they query the
+# device, so the codes (and intmcp_create's reason) are checked without a GPU.
+_TABLE = (ctypes.c_double * 8)(*[0.0] * 8)
+
+
+def _valid_configs():
+    """(pomcp_config, intmcp_config) of a small Driving engine."""
+    from posggym_baselines_amd.envs import DrivingModel
+    pc, ic = N.PomcpConfig(), N.IntmcpConfig()
+    for c, sel in ((pc, N.SEL_PUCB), (ic.base, N.SEL_UCB)):
+        c.abi_version = N.POMCP_ABI_VERSION
+        c.num_agents, c.ego_agent, c.num_actions = 2, 0, 5
+        c.action_selection = sel
+        c.depth_limit, c.step_limit = 2, 50
+        c.num_particles, c.extra_particles = 8, 2
+        c.num_trees = 1
+        c.discount, c.c = 0.95, 1.4
+        c.pucb_exploration_fraction = 0.25
+        c.reinvigoration_sample_limit_factor = 4.0
+        c.max_blocks, c.max_particles, c.max_belief, c.overflow_slots = 64, 1024, 256, 16
+        c.log_table, c.log_table_size = _TABLE, 8
+        c.discount_pow, c.discount_pow_size = _TABLE, 8
+        DrivingModel().configure_engine(c)
+    ic.nesting_level = 1
+    ic.max_nodes, ic.max_stats, ic.max_log, ic.hash_slots = 256, 1280, 256, 512
+    ic.max_root_belief, ic.max_support_particles = 256, 1024
+    return pc, ic
+
+
+def _create(name, cfg):
+    """(return code, *out) of pomcp_create / intmcp_create; a context that a
+    valid configuration gives on a machine with a GPU is destroyed."""
+    lib = N.load()
+    out = ctypes.c_void_p(0xDEAD)   # must be overwritten with NULL on failure
+    rc = getattr(lib, name + "_create")(ctypes.byref(cfg) if cfg is not None else None, 0, None,
+                                        ctypes.byref(out))
+    if rc == N.POMCP_OK:
+        getattr(lib, name + "_destroy")(out)
+    return rc, out.value
+
+
+def _break(cfg, field, value):
+    base = cfg.base if isinstance(cfg, N.IntmcpConfig) and not hasattr(cfg, field) else cfg
+    setattr(base, field, value)
+    return cfg
+
+
+_NO_TABLE = ctypes.POINTER(ctypes.c_double)()
+POMCP_CREATE_ERRORS = [
+    ("abi_version", N.POMCP_ABI_VERSION + 1, N.POMCP_E_INVALID),
+    ("env_id", 99, N.POMCP_E_UNSUPPORTED),
+    ("num_agents", 3, N.POMCP_E_UNSUPPORTED),
+    ("num_actions", 4, N.POMCP_E_INVALID),
+    ("discount", 1.5, N.POMCP_E_INVALID),
+    ("overflow_slots", 48, N.POMCP_E_INVALID),
+    ("log_table", _NO_TABLE, N.POMCP_E_INVALID),
+]
+INTMCP_CREATE_ERRORS = [
+    ("abi_version", N.POMCP_ABI_VERSION + 1, N.POMCP_E_INVALID, "ABI version mismatch"),
+    ("env_id", 99, N.POMCP_E_UNSUPPORTED, "env_id"),
+    ("num_agents", 3, N.POMCP_E_UNSUPPORTED, "2 agents"),
+    ("num_actions", 4, N.POMCP_E_INVALID, "num_actions"),
+    ("hash_slots", 48, N.POMCP_E_INVALID, "capacities"),
+    ("nesting_level", 6, N.POMCP_E_UNSUPPORTED, "nesting levels 0 to INTMCP_MAX_TREES - 1 (5)"),
+    ("log_table", _NO_TABLE, N.POMCP_E_INVALID, "tables"),
+]
+
+
+def test_valid_create_configs_pass_validation():
+    """The configurations the error cases break one field of are valid: create
+    gets as far as the device (no GPU: POMCP_E_NO_DEVICE)."""
+    pc, ic = _valid_configs()
+    assert _create("pomcp", pc)[0] in (N.POMCP_OK, N.POMCP_E_NO_DEVICE)
+    rc = _create("intmcp", ic)[0]
+    assert rc in (N.POMCP_OK, N.POMCP_E_NO_DEVICE)
+    assert N.load().intmcp_last_error(None) == b""
+
+
+@pytest.mark.parametrize("field,value,code", POMCP_CREATE_ERRORS,
+                         ids=[e[0] for e in POMCP_CREATE_ERRORS])
+def test_pomcp_create_rejects_a_bad_config(field, value, code):
+    rc, out = _create("pomcp", _break(_valid_configs()[0], field, value))
+    assert rc == code
+    assert out is None
+
+
+@pytest.mark.parametrize("field,value,code,why", INTMCP_CREATE_ERRORS,
+                         ids=[e[0] for e in INTMCP_CREATE_ERRORS])
+def test_intmcp_create_rejects_a_bad_config(field, value, code, why):
+    rc, out = _create("intmcp", _break(_valid_configs()[1], field, value))
+    assert rc == code
+    assert out is None
+    assert N.load().intmcp_last_error(None) == why.encode()
+
+
+def test_create_rejects_a_null_config():
+    assert _create("pomcp", None) == (N.POMCP_E_INVALID, 0xDEAD)   # (*out is not touched)
+    assert _create("intmcp", None) == (N.POMCP_E_INVALID, 0xDEAD)
+    assert N.load().pomcp_last_error(None) == b"null context"
