@@ -609,6 +609,66 @@ int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_ind
                           int32_t other_action, const double* other_pi, int32_t num_other,
                           double out[3]);
 
+/* ---- Episode queue (ABI 7, additive; csrc/pomcp_episode_queue.hip) ----------
+ * n >= num_trees episodes on the context's num_trees slots: a tree whose
+ * episode ends takes the next environment seed of a device-resident queue
+ * instead of staying parked.  The assignment rule: slot b starts with entry b
+ * and next = num_trees; at the end of each pomcp_episodes_step the slots whose
+ * episode finished in that step take entries next, next + 1, ... in ascending
+ * slot order while entries remain; a slot that finds the queue empty is retired
+ * (parked as a finished tree is, its last real search's root statistics kept).
+ * A refilled tree is reset as pomcp_reset resets it (its RNG stream counters
+ * carry on, as over planner.reset() in the serial harness) and its records
+ * leave its search wave's shared particle log (k_log_drop) while the wave's
+ * other trees are mid-episode. */
+typedef struct pomcp_episode_queue_row {
+  pomcp_episode_result res;      /* the episode's row */
+  int32_t slot;                  /* the tree that played it */
+  int32_t slot_order;            /* its ordinal among that tree's episodes */
+  int32_t policy_index;          /* pomcp_episode_pop_state.policy_index of the episode */
+  int32_t start_step;            /* the pomcp_episodes_step call (from 0) it started at */
+  pomcp_episode_belief_acc acc;  /* zero unless pomcp_episodes_track_belief_acc */
+} pomcp_episode_queue_row;
+
+/* pomcp_episodes_begin on env_seeds[0 .. num_trees), then queue mode: env_seeds
+ * has n >= num_trees entries (copied).  pomcp_episodes_begin and pomcp_reset end
+ * queue mode.  The per-step accuracy table is not kept in queue mode. */
+int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
+                               const double* pow_table, int32_t max_steps, int32_t until);
+/* While a queue is active pomcp_episodes_step also ranks the finished slots,
+ * writes their rows, refills or retires them and drops the refilled trees' log
+ * records; its live_out is then unfinished + refilled slots (0: every entry
+ * has been played). */
+/* The rows (host, [n], queue order); the row of an entry that has not finished
+ * is zero. */
+int pomcp_episodes_queue_rows(pomcp_ctx* ctx, pomcp_episode_queue_row* out);
+/* The entry each slot is playing (host, [num_trees]); -1: retired. */
+int pomcp_episodes_queue_slots(pomcp_ctx* ctx, int32_t* out);
+/* The episodes that ended in the last pomcp_episodes_step (host, [num_trees]
+ * each): queue_index_out[b] = the entry that ended in slot b, else -1, and
+ * states_out[b] = its whole final record (unspecified for -1) -- the slot's own
+ * record is the next episode's by then. */
+int pomcp_episodes_queue_finished(pomcp_ctx* ctx, pomcp_episode_state* states_out,
+                                  int32_t* queue_index_out);
+/* Device time (ms) since pomcp_episodes_queue_begin: ms[0] the rank and refill
+ * kernels, ms[1] k_log_drop (both taken out of pomcp_episodes_timing's ms[2]). */
+int pomcp_episodes_queue_timing(pomcp_ctx* ctx, double ms[2]);
+
+/* Host twins (csrc/episode_queue.h: the kernels' per-record and per-slot
+ * decisions).  pomcp_host_log_drop: k_log_drop on a log given as structure of
+ * arrays (aux may be NULL), in place: the records whose tree lane (id >> 26) is
+ * in lane_mask leave, the others keep their order; *count_out = records kept.
+ * pomcp_host_queue_assign: one step of the assignment rule.  queue_index[b]:
+ * the entry slot b plays (-1: retired), finished[b]: its episode record's
+ * flag; assign_out[b] = the slot's new entry, -1 (retired now) or -2 (plays
+ * on, or was retired before); *next_io is advanced; *refilled_out = slots
+ * refilled. */
+int pomcp_host_log_drop(uint32_t* ids, uint32_t* v0, uint32_t* v1, uint32_t* aux, int64_t n,
+                        uint64_t lane_mask, int64_t* count_out);
+int pomcp_host_queue_assign(const int32_t* queue_index, const int32_t* finished,
+                            int32_t num_slots, int32_t n, int32_t* next_io, int32_t* assign_out,
+                            int32_t* refilled_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,16 @@ int pomcp_debug_belief_stats_ms(pomcp_ctx* ctx, const uint32_t* states, int32_t 
  * limit (also when POMCP_SEARCH_DEPTH_SPEC=0 is set in the environment, or the
  * launch goes to the wave-per-tree kernel).  Results are the same either way. */
 int pomcp_debug_search_depth_spec(const pomcp_ctx* ctx);
+/* One search wave's shared particle log (trees 64 wave .. 64 wave + 63) in
+ * record order: *count = its records, of which the first min(count, capacity)
+ * go to ids / v0 / v1 (and aux, on a type-based context; NULL: not wanted).
+ * A record's tree lane is ids[i] >> 26. */
+int pomcp_debug_get_wave_log(pomcp_ctx* ctx, int32_t wave, uint32_t* ids, uint32_t* v0, uint32_t* v1,
+                             uint32_t* aux, int32_t capacity, int32_t* count);
+/* Launches k_log_drop with the caller's masks (one uint64 per search wave: bit
+ * l = drop the records of tree lane l).  The trees' own log counts are not
+ * touched: a test of the kernel, not a way to reset a tree. */
+int pomcp_debug_log_drop(pomcp_ctx* ctx, const uint64_t* masks);
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@
 
 #include "belief_stats.h"
 #include "driving.h"
+#include "episode_queue.h"
 #include "episode_step.h"
 #include "host_exp.h"
 #include "philox.h"
@@ -308,6 +309,48 @@ int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_ind
   bel_accuracy(counts->belief_size, counts->state_matches < 0 ? 0 : counts->state_matches,
                counts->policy_hist, num_other, mixture_index, other_action, other_pi,
                POMCP_MAX_ACTIONS, out);
+  return POMCP_OK;
+}
+
+// ------------------------------------------------------- host episode queue
+
+// k_log_drop's decision per record (episode_queue.h log_drop_keeps), the kept
+// records moved down in order.
+int pomcp_host_log_drop(uint32_t* ids, uint32_t* v0, uint32_t* v1, uint32_t* aux, int64_t n,
+                        uint64_t lane_mask, int64_t* count_out) {
+  if (n < 0 || !count_out || (n > 0 && (!ids || !v0 || !v1))) return POMCP_E_INVALID;
+  int64_t out = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!log_drop_keeps(ids[i], lane_mask)) continue;
+    if (out != i) {
+      ids[out] = ids[i];
+      v0[out] = v0[i];
+      v1[out] = v1[i];
+      if (aux) aux[out] = aux[i];
+    }
+    ++out;
+  }
+  *count_out = out;
+  return POMCP_OK;
+}
+
+// k_queue_rank's decisions (episode_queue.h), the slots in ascending order.
+int pomcp_host_queue_assign(const int32_t* queue_index, const int32_t* finished,
+                            int32_t num_slots, int32_t n, int32_t* next_io, int32_t* assign_out,
+                            int32_t* refilled_out) {
+  if (!queue_index || !finished || !next_io || !assign_out || !refilled_out || num_slots < 1 ||
+      n < num_slots || *next_io < num_slots || *next_io > n)
+    return POMCP_E_INVALID;
+  const int32_t next = *next_io;
+  int32_t done = 0;
+  for (int32_t b = 0; b < num_slots; ++b) {
+    const bool f = queue_slot_finished(queue_index[b], finished[b]);
+    assign_out[b] = f ? queue_assign(done, next, n) : kQueuePlaying;
+    done += f ? 1 : 0;
+  }
+  const int32_t r = queue_refilled(done, next, n);
+  *next_io = next + r;
+  *refilled_out = r;
   return POMCP_OK;
 }
 

@@ -22,6 +22,7 @@
 #include "belief_stats.hip"
 #include "pomcp_episode.hip"
 #include "episode_belief_acc.hip"
+#include "pomcp_episode_queue.hip"
 #include "pomcp_search.hip"
 #include "pomcp_search_lds.hip"
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
@@ -95,6 +96,15 @@ struct pomcp_ctx : HostCtx {
   int64_t acc_steps_cap = 0;
   double host_other_pi[kTmMax][POMCP_MAX_ACTIONS] = {};   // pomcp_type_policies.other_pi
   double ep_acc_ms = 0.0;
+  // the episode queue (pomcp_episodes_queue_begin): whether the running batch
+  // has one, its device state and the capacity of its per-entry arrays, the
+  // device time of its kernels ({rank + refill, k_log_drop}) and their events
+  bool q_active = false;
+  EpQueueDev q{};
+  int32_t q_cap = 0;
+  double q_ms[2] = {0.0, 0.0};
+  hipEvent_t q_ev[3] = {nullptr, nullptr, nullptr};
+  uint64_t* drop_masks = nullptr;   // [search waves] (also pomcp_debug_log_drop's)
 };
 
 // Wave-per-tree search (k_search_lds) for batches up to this many trees: one
@@ -349,6 +359,8 @@ void pomcp_destroy(pomcp_ctx* ctx) {
   if (ctx->snap_hdr) (void)hipFree(ctx->snap_hdr);
   for (hipEvent_t e : ctx->ep_ev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->q_ev)
+    if (e) (void)hipEventDestroy(e);
   delete ctx;
 }
 
@@ -361,6 +373,7 @@ int pomcp_reset(pomcp_ctx* ctx) {
   ctx->defer_pending = false;
   ctx->have_root = false;
   ctx->ep_active = false;   // a batch of episodes ends with its trees
+  ctx->q_active = false;    // and its queue
   return POMCP_OK;
 }
 
@@ -1109,7 +1122,7 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     ep.acc_nparts = nparts;
   }
   ctx->ep_active = false;
-  if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;
+  if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;   // (ends queue mode too)
   if ((rc = ctx->upload(ep.env_seeds, env_seeds, nB)) != POMCP_OK ||
       (rc = ctx->upload(ep.pow_table, pow_table, (size_t)max_steps)) != POMCP_OK)
     return rc;
@@ -1158,12 +1171,35 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     PB_TRY(ctx, hipGetLastError());
     PB_TRY(ctx, hipEventRecord(ctx->ep_ev[5], ctx->stream));
   }
+  if (ctx->q_active) {
+    // the queue: the finished slots ranked, their rows written, the slots
+    // refilled or retired, the refilled trees' records out of the shared logs
+    // (before the next update's scan and the new episodes' first appends)
+    ctx->q.step = ctx->ep_steps;
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_queue_rank, dim3(1), dim3(kRankThreads), 0, ctx->stream, ctx->ep, ctx->q, B);
+    PB_TRY(ctx, hipGetLastError());
+    with_episode_env(ctx, [&](auto e) {
+      hipLaunchKernelGGL(k_queue_refill<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
+                         ctx->dp, ctx->ep, ctx->q);
+    });
+    PB_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[1], ctx->stream));
+    hipLaunchKernelGGL(k_log_drop, dim3((unsigned)search_waves(B)), dim3(kDropThreads), 0, ctx->stream,
+                       ctx->dp, (const uint64_t*)ctx->drop_masks);
+    PB_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[2], ctx->stream));
+  }
   hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
   PB_TRY(ctx, hipGetLastError());
   PB_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
   int32_t counts[2] = {0, 0};
   PB_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
                              ctx->stream));
+  int32_t qstate[2] = {0, 0};   // {next, slots refilled this step}
+  if (ctx->q_active)
+    PB_TRY(ctx, hipMemcpyAsync(qstate, ctx->q.state, sizeof(qstate), hipMemcpyDeviceToHost,
+                               ctx->stream));
   uint32_t lf_fail = 0u;
   if (reroot && !ctx->log_scan_legacy)
     PB_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
@@ -1181,8 +1217,16 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     ctx->ep_acc_ms += (double)ms;
     ctx->ep_ms[2] -= (double)ms;
   }
+  if (ctx->q_active) {   // their own figures, not a part of slot 2
+    for (int k = 0; k < 2; ++k) {
+      float ms = 0.f;
+      PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->q_ev[k], ctx->q_ev[k + 1]));
+      ctx->q_ms[k] += (double)ms;
+      ctx->ep_ms[2] -= (double)ms;
+    }
+  }
   if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
-  *live_out = counts[0];
+  *live_out = counts[0] + qstate[1];   // (a refilled slot plays on)
   if (counts[1] != 0) {   // some tree failed: the update's error first, then the search's
     if ((rc = ctx->fetch(ctx->host_upd.data(), ctx->dp.upd_out, 2 * (size_t)B)) != POMCP_OK ||
         (rc = first_update_error(ctx)) != POMCP_OK ||
@@ -1302,6 +1346,146 @@ int pomcp_episodes_timing(pomcp_ctx* ctx, double ms[3], int32_t* steps) {
   if (!ctx || !ms || !steps) return POMCP_E_INVALID;
   for (int k = 0; k < 3; ++k) ms[k] = ctx->ep_ms[k];
   *steps = ctx->ep_steps;
+  return POMCP_OK;
+}
+
+// ------------------------------------------------------------ episode queue
+
+static int ensure_drop_masks(pomcp_ctx* ctx) {
+  if (ctx->drop_masks) return POMCP_OK;
+  return ctx->alloc(ctx->drop_masks, (size_t)search_waves(ctx->dp.B));
+}
+
+int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
+                               const double* pow_table, int32_t max_steps, int32_t until) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!env_seeds || n < ctx->dp.B)
+    return fail(ctx, POMCP_E_INVALID, "episodes_queue_begin: the queue needs at least num_trees "
+                                      "environment seeds");
+  const bool steps_want = ctx->ep_acc_steps_want;
+  ctx->ep_acc_steps_want = false;   // (no per-step table in queue mode)
+  int rc = pomcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);
+  ctx->ep_acc_steps_want = steps_want;
+  if (rc != POMCP_OK) return rc;
+  const int B = ctx->dp.B;
+  const size_t nB = (size_t)B;
+  EpQueueDev& q = ctx->q;
+  for (hipEvent_t& e : ctx->q_ev)
+    if (!e) PB_TRY(ctx, hipEventCreate(&e));
+  if ((rc = ensure_drop_masks(ctx)) != POMCP_OK) return rc;
+  if (!q.fin_q) {   // (the last one allocated)
+    if ((rc = ctx->alloc(q.slot_q, nB)) != POMCP_OK || (rc = ctx->alloc(q.slot_ord, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(q.slot_start, nB)) != POMCP_OK || (rc = ctx->alloc(q.assign, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(q.state, 2)) != POMCP_OK || (rc = ctx->alloc(q.fin, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(q.fin_q, nB)) != POMCP_OK)
+      return rc;
+  }
+  if (n > ctx->q_cap) {   // (an earlier, shorter queue stays allocated until the context goes)
+    ctx->q_cap = 0;
+    if ((rc = ctx->alloc(q.seeds, (size_t)n)) != POMCP_OK ||
+        (rc = ctx->alloc(q.rows, (size_t)n)) != POMCP_OK)
+      return rc;
+    ctx->q_cap = n;
+  }
+  q.drop = ctx->drop_masks;
+  q.acc_in = ctx->ep_acc ? ctx->acc.rec : nullptr;
+  q.acc = ctx->ep_acc ? ctx->acc.rec : nullptr;
+  q.n = n;
+  q.step = 0;
+  std::vector<int32_t> iota(nB), minus(nB, -1);
+  for (int b = 0; b < B; ++b) iota[(size_t)b] = b;
+  const int32_t state[2] = {B, 0};
+  if ((rc = ctx->upload(q.seeds, env_seeds, (size_t)n)) != POMCP_OK ||
+      (rc = ctx->upload(q.slot_q, iota.data(), nB)) != POMCP_OK ||
+      (rc = ctx->upload(q.fin_q, minus.data(), nB)) != POMCP_OK ||
+      (rc = ctx->upload(q.state, state, 2)) != POMCP_OK)
+    return rc;
+  PB_TRY(ctx, hipMemsetAsync(q.slot_ord, 0, sizeof(int32_t) * nB, ctx->stream));
+  PB_TRY(ctx, hipMemsetAsync(q.slot_start, 0, sizeof(int32_t) * nB, ctx->stream));
+  PB_TRY(ctx, hipMemsetAsync(q.rows, 0, sizeof(pomcp_episode_queue_row) * (size_t)n, ctx->stream));
+  PB_TRY(ctx, hipMemsetAsync(ctx->drop_masks, 0, sizeof(uint64_t) * (size_t)search_waves(B),
+                             ctx->stream));
+  // (copied from the caller's and local memory: finish before returning)
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->q_ms[0] = ctx->q_ms[1] = 0.0;
+  ctx->q_active = true;
+  return POMCP_OK;
+}
+
+static int queue_ready(pomcp_ctx* ctx, const char* what) {
+  if (!ctx->ep_active || !ctx->q_active)
+    return fail(ctx, POMCP_E_STATE, std::string(what) + ": pomcp_episodes_queue_begin first");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return POMCP_OK;
+}
+
+int pomcp_episodes_queue_rows(pomcp_ctx* ctx, pomcp_episode_queue_row* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  const int rc = queue_ready(ctx, "episodes_queue_rows");
+  return rc != POMCP_OK ? rc : ctx->fetch(out, (const pomcp_episode_queue_row*)ctx->q.rows,
+                                          (size_t)ctx->q.n);
+}
+
+int pomcp_episodes_queue_slots(pomcp_ctx* ctx, int32_t* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  const int rc = queue_ready(ctx, "episodes_queue_slots");
+  return rc != POMCP_OK ? rc : ctx->fetch(out, (const int32_t*)ctx->q.slot_q, (size_t)ctx->dp.B);
+}
+
+int pomcp_episodes_queue_finished(pomcp_ctx* ctx, pomcp_episode_state* states_out,
+                                  int32_t* queue_index_out) {
+  if (!ctx || !states_out || !queue_index_out) return POMCP_E_INVALID;
+  int rc = queue_ready(ctx, "episodes_queue_finished");
+  if (rc != POMCP_OK) return rc;
+  if ((rc = ctx->fetch(queue_index_out, (const int32_t*)ctx->q.fin_q, (size_t)ctx->dp.B)) != POMCP_OK)
+    return rc;
+  return ctx->fetch(states_out, (const pomcp_episode_state*)ctx->q.fin, (size_t)ctx->dp.B);
+}
+
+int pomcp_episodes_queue_timing(pomcp_ctx* ctx, double ms[2]) {
+  if (!ctx || !ms) return POMCP_E_INVALID;
+  ms[0] = ctx->q_ms[0];
+  ms[1] = ctx->q_ms[1];
+  return POMCP_OK;
+}
+
+// Debug: one search wave's log, in record order (pomcp_device.h WaveLog).
+int pomcp_debug_get_wave_log(pomcp_ctx* ctx, int32_t wave, uint32_t* ids, uint32_t* v0, uint32_t* v1,
+                             uint32_t* aux, int32_t capacity, int32_t* count) {
+  if (!ctx || !count || wave < 0 || wave >= search_waves(ctx->dp.B) || capacity < 0)
+    return POMCP_E_INVALID;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  uint32_t n = 0u;
+  int rc = ctx->fetch(&n, (const uint32_t*)ctx->dp.wlog + wave, 1);
+  if (rc != POMCP_OK) return rc;
+  const int64_t cap = (int64_t)kWave * ctx->dp.Np;
+  if ((int64_t)n > cap || n > (uint32_t)INT32_MAX)
+    return fail(ctx, POMCP_E_STATE, "get_wave_log: a count beyond the log's capacity");
+  *count = (int32_t)n;
+  const size_t m = (size_t)((int32_t)n < capacity ? (int32_t)n : capacity);
+  if (m == 0) return POMCP_OK;
+  if (!ids || !v0 || !v1) return POMCP_E_INVALID;
+  if (aux && !ctx->dp.tm) return fail(ctx, POMCP_E_STATE, "get_wave_log: aux needs a type-based context");
+  const uint32_t* base = reinterpret_cast<const uint32_t*>(ctx->dp.plog) +
+                         (int64_t)wave * (3 + ctx->dp.tm) * cap;
+  if ((rc = ctx->fetch(ids, base, m)) != POMCP_OK || (rc = ctx->fetch(v0, base + cap, m)) != POMCP_OK ||
+      (rc = ctx->fetch(v1, base + 2 * cap, m)) != POMCP_OK)
+    return rc;
+  return aux ? ctx->fetch(aux, base + 3 * cap, m) : POMCP_OK;
+}
+
+// Debug: k_log_drop with the caller's masks.
+int pomcp_debug_log_drop(pomcp_ctx* ctx, const uint64_t* masks) {
+  if (!ctx || !masks) return POMCP_E_INVALID;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_drop_masks(ctx);
+  if (rc != POMCP_OK) return rc;
+  const int nsw = search_waves(ctx->dp.B);
+  if ((rc = ctx->upload((const uint64_t*)ctx->drop_masks, masks, (size_t)nsw)) != POMCP_OK) return rc;
+  hipLaunchKernelGGL(k_log_drop, dim3((unsigned)nsw), dim3(kDropThreads), 0, ctx->stream, ctx->dp,
+                     (const uint64_t*)ctx->drop_masks);
+  PB_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (`masks` is the caller's memory)
   return POMCP_OK;
 }
 

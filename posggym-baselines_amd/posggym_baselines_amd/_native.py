@@ -272,6 +272,18 @@ class PomcpEpisodeBeliefAcc(C.Structure):
     ]
 
 
+class PomcpEpisodeQueueRow(C.Structure):
+    """``pomcp_episode_queue_row`` (include/pomcp.h)."""
+    _fields_ = [
+        ("res", PomcpEpisodeResult),
+        ("slot", C.c_int32),
+        ("slot_order", C.c_int32),
+        ("policy_index", C.c_int32),
+        ("start_step", C.c_int32),
+        ("acc", PomcpEpisodeBeliefAcc),
+    ]
+
+
 EPISODE_POP_STATE_DTYPE = [("policy_index", "<i4"), ("mixture_index", "<i4")]
 EPISODE_BELIEF_ACC_DTYPE = [("state_sum", "<f8"), ("policy_sum", "<f8"), ("action_sum", "<f8"),
                             ("count", "<i4"), ("error", "<i4")]
@@ -286,6 +298,9 @@ EPISODE_STATE_DTYPE = [("res", EPISODE_RESULT_DTYPE), ("v0", "<u4"), ("v1", "<u4
                        ("model_ctr", "<u4"), ("policy_ctr", "<u4"), ("last_action", "<i4"),
                        ("finished", "<i4"), ("root_absorbing", "<i4"),
                        ("last_other_action", "<i4"), ("last_reward", "<f8")]
+EPISODE_QUEUE_ROW_DTYPE = [("res", EPISODE_RESULT_DTYPE), ("slot", "<i4"), ("slot_order", "<i4"),
+                           ("policy_index", "<i4"), ("start_step", "<i4"),
+                           ("acc", EPISODE_BELIEF_ACC_DTYPE)]
 
 
 # (name, restype, argtypes) for every symbol include/pomcp.h declares.
@@ -383,6 +398,14 @@ SIGNATURES = [
       C.POINTER(PomcpEpisodeState), C.POINTER(PomcpEpisodeStepOut)]),
     ("pomcp_host_belief_acc", C.c_int,
      [C.POINTER(PomcpBeliefCounts), C.c_int32, C.c_int32, _PD, C.c_int32, _PD]),
+    ("pomcp_episodes_queue_begin", C.c_int, [_CTX, _PU64, C.c_int32, _PD, C.c_int32, C.c_int32]),
+    ("pomcp_episodes_queue_rows", C.c_int, [_CTX, C.POINTER(PomcpEpisodeQueueRow)]),
+    ("pomcp_episodes_queue_slots", C.c_int, [_CTX, _P32]),
+    ("pomcp_episodes_queue_finished", C.c_int, [_CTX, C.POINTER(PomcpEpisodeState), _P32]),
+    ("pomcp_episodes_queue_timing", C.c_int, [_CTX, _PD]),
+    ("pomcp_host_log_drop", C.c_int,
+     [_PU32, _PU32, _PU32, _PU32, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
+    ("pomcp_host_queue_assign", C.c_int, [_P32, _P32, C.c_int32, C.c_int32, _P32, _P32, _P32]),
 ]
 DEBUG_SIGNATURES = [
     ("pomcp_debug_fp_selftest", C.c_int, [_PD, _PD, C.c_int32, _PD]),
@@ -397,6 +420,9 @@ DEBUG_SIGNATURES = [
     ("pomcp_debug_belief_stats_ms", C.c_int,
      [C.c_void_p, _PU32, C.c_int32, C.POINTER(C.c_float)]),
     ("pomcp_debug_search_depth_spec", C.c_int, [C.c_void_p]),
+    ("pomcp_debug_get_wave_log", C.c_int,
+     [C.c_void_p, C.c_int32, _PU32, _PU32, _PU32, _PU32, C.c_int32, _P32]),
+    ("pomcp_debug_log_drop", C.c_int, [C.c_void_p, _PU64]),
     ("intmcp_debug_set_softmax_slack", C.c_int, [C.c_void_p, C.c_float]),
     ("intmcp_debug_exact_draws", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 ]

@@ -589,6 +589,79 @@ class PomcpEngine(EngineBase):
         self._check(self._lib.pomcp_episodes_timing(self._ctx, ms, C.byref(n)), "episodes_timing")
         return (ms[0], ms[1], ms[2]), n.value
 
+    # ------------------------------------------------- episode queue
+    def episodes_queue_begin(self, env_seeds, pow_table, max_steps, until, track_states=False):
+        """``episodes_begin`` on the first ``num_trees`` seeds, then queue mode
+        (``pomcp_episodes_queue_begin``): a tree whose episode ends takes the next
+        of ``env_seeds`` (at least ``num_trees`` of them) on the device."""
+        seeds = np.ascontiguousarray(np.asarray(env_seeds, dtype=np.uint64).reshape(-1))
+        if len(seeds) < self.num_trees:
+            raise ValueError(f"an episode queue needs at least {self.num_trees} seeds")
+        pw = np.ascontiguousarray(np.asarray(pow_table, dtype=np.float64))
+        if len(pw) < int(max_steps):
+            raise ValueError("pow_table needs max_steps entries")
+        mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
+        self._check(self._lib.pomcp_episodes_track_states(self._ctx, 1 if track_states else 0),
+                    "episodes_track_states")
+        self._check(self._lib.pomcp_episodes_queue_begin(
+            self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), len(seeds),
+            pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_queue_begin")
+        self._queue_len = len(seeds)
+
+    def episodes_queue_rows(self):
+        """Every queue entry's ``pomcp_episode_queue_row``, in queue order (zero
+        for an entry that has not finished)."""
+        n = getattr(self, "_queue_len", 0)   # (0: no queue was begun; the call says so)
+        out = np.zeros(max(n, 1), dtype=N.EPISODE_QUEUE_ROW_DTYPE)
+        self._check(self._lib.pomcp_episodes_queue_rows(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeQueueRow))), "episodes_queue_rows")
+        return out[:n]
+
+    def episodes_queue_slots(self):
+        """The queue entry each tree is playing (-1: retired)."""
+        out = np.zeros(self.num_trees, dtype=np.int32)
+        self._check(self._lib.pomcp_episodes_queue_slots(
+            self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_slots")
+        return out
+
+    def episodes_queue_finished(self):
+        """The episodes that ended in the last step: per tree the queue entry
+        (-1: none) and its final ``pomcp_episode_state``."""
+        idx = np.zeros(self.num_trees, dtype=np.int32)
+        st = np.zeros(self.num_trees, dtype=N.EPISODE_STATE_DTYPE)
+        self._check(self._lib.pomcp_episodes_queue_finished(
+            self._ctx, st.ctypes.data_as(C.POINTER(N.PomcpEpisodeState)),
+            idx.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_finished")
+        return idx, st
+
+    def episodes_queue_timing(self):
+        """Device milliseconds since ``episodes_queue_begin`` spent in (the rank and
+        refill kernels, ``k_log_drop``)."""
+        ms = (C.c_double * 2)()
+        self._check(self._lib.pomcp_episodes_queue_timing(self._ctx, ms), "episodes_queue_timing")
+        return ms[0], ms[1]
+
+    def debug_wave_log(self, wave):
+        """One search wave's shared particle log in record order
+        (``pomcp_debug_get_wave_log``): (ids, v0, v1, aux or None)."""
+        lib = self._lib
+        n = C.c_int32()
+        self._check(lib.pomcp_debug_get_wave_log(self._ctx, int(wave), None, None, None, None, 0,
+                                                 C.byref(n)), "debug_get_wave_log")
+        tm = self.type_based
+        arrs = [np.zeros(n.value, dtype=np.uint32) for _ in range(4 if tm else 3)]
+        ptrs = [a.ctypes.data_as(C.POINTER(C.c_uint32)) for a in arrs] + ([] if tm else [None])
+        self._check(lib.pomcp_debug_get_wave_log(self._ctx, int(wave), *ptrs, n.value, C.byref(n)),
+                    "debug_get_wave_log")
+        return arrs[0], arrs[1], arrs[2], (arrs[3] if tm else None)
+
+    def debug_log_drop(self, masks):
+        """``k_log_drop`` with one 64-bit lane mask per search wave
+        (``pomcp_debug_log_drop``)."""
+        m = np.ascontiguousarray(np.asarray(masks, dtype=np.uint64).reshape((self.num_trees + 63) // 64))
+        self._check(self._lib.pomcp_debug_log_drop(
+            self._ctx, m.ctypes.data_as(C.POINTER(C.c_uint64))), "debug_log_drop")
+
     def snapshot(self):
         self._check(self._lib.pomcp_snapshot(self._ctx), "snapshot")
 

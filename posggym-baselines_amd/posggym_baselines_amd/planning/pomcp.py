@@ -607,6 +607,133 @@ class BatchedPOMCP:
             rows.append(row)
         return rows
 
+    def run_episode_queue(self, env_seeds, *, until: str = "agent_done", other_agents=None,
+                          belief_acc=False, belief_states: bool = False, write_row=None,
+                          on_step=None):
+        """Play ``N = len(env_seeds)`` episodes (``N >= num_trees``) on the batch's
+        ``num_trees`` slots; returns ``N`` rows in queue order.
+
+        ``run_episodes`` parks a tree whose episode ends until the slowest one
+        of the batch is over; here it takes the next seed of a queue that lives
+        on the device (``pomcp_episodes_queue_begin``), so every slot plays until
+        ``N`` episodes have been handed out.  The assignment rule: slot ``b``
+        starts with entry ``b`` and ``next = num_trees``; at the end of each
+        batch step the slots whose episode finished in that step take entries
+        ``next, next + 1, ...`` in ascending slot order while entries remain; a
+        slot that finds the queue empty is retired (parked as a finished tree
+        is, its last real search's root statistics kept).
+
+        Parity: the episodes slot ``b`` plays, in order, are bit for bit the
+        episodes ``run_planning_episodes`` plays over their seeds on one planner
+        keyed ``(seed, tree_key_base + b)``: the tree is reset between them as
+        ``planner.reset()`` resets it and its RNG streams carry on.
+
+        Row keys: ``run_episodes``' plus ``slot`` and ``slot_order`` (the
+        episode's ordinal within its slot); ``num`` is the queue index;
+        ``time`` / ``search_time`` / ``update_time`` are the whole call's and the
+        batch's per-step figures.  ``until``, ``other_agents``, ``belief_acc``
+        (the per-episode means; there is no per-step table in queue mode),
+        ``belief_states``, ``write_row`` and ``on_step(t, self)`` are
+        ``run_episodes``'.  For ``on_step``: ``episode_queue_slots()`` is the
+        entry each slot is playing, and ``episode_queue_finished()`` the final
+        records of the episodes that ended in the step just played (their
+        slots' ``episode_states()`` are the next episodes' by then).
+        """
+        from posggym_baselines_amd.planning.episodes import EPISODE_RESULT_HEADS
+        if until not in ("agent_done", "all_done"):
+            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        B = self.num_trees
+        seeds = [int(s) for s in env_seeds]
+        N = len(seeds)
+        if N < B:
+            raise ValueError(f"run_episode_queue needs at least {B} env_seeds (one per tree), "
+                             f"not {N}")
+        spec = getattr(self.engine.model, "spec", None)
+        max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
+        if max_steps < 1:
+            raise ValueError("run_episode_queue needs the model's spec.max_episode_steps")
+        if self._planned is not None:
+            searches, reroot = self._planned
+            if not reroot or searches < max_steps:
+                raise ValueError(
+                    f"run_episode_queue re-roots up to {max_steps} times per episode: create the "
+                    f"engine with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one "
+                    f"was sized with searches={searches}, reroot={reroot})")
+        acc_stats = self._belief_acc_stats(belief_acc)
+        pop_ids = pop_probs = mix = None
+        if other_agents is not None:
+            from posggym_baselines_amd.planning.episodes import check_population
+            other_agents = list(other_agents)
+            pop_probs = check_population(other_agents, self.engine.A)
+            pop_ids = [pol.policy_id for pol in other_agents]
+            known = self.other_policy_ids or []
+            mix = [known.index(i) if i in known else -1 for i in pop_ids]
+        gamma = self.engine.config.discount
+        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
+        start = time.time()
+        self.engine.episodes_set_population(pop_probs, mix)
+        self.engine.episodes_track_belief_acc(bool(acc_stats), False)
+        self.engine.episodes_queue_begin(seeds, pow_table, max_steps, until,
+                                         track_states=belief_states)
+        live, t = B, 0
+        while live > 0 and t < N * max_steps:
+            live = self.engine.episodes_step(self.num_sims)
+            if on_step is not None:
+                on_step(t, self)
+            t += 1
+        if live > 0:
+            raise RuntimeError(f"run_episode_queue: {live} slots still playing after {t} steps")
+        res = self.engine.episodes_queue_rows()
+        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
+        elapsed = time.time() - start
+        mem = psutil.Process().memory_info().rss / 1024**2
+        acc_columns = []
+        if acc_stats:
+            from posggym_baselines_amd.planning.utils import BeliefStatTracker
+            acc = res["acc"]
+            cnt = acc["count"].astype(np.int64)
+            for key in BeliefStatTracker.get_stat_keys(acc_stats, False, max_steps):
+                k = key[len("belief_"):-len("_acc")]
+                # sum / count is one IEEE division, as Python's
+                v = 0.0 if k == "history" else acc[k + "_sum"] / np.maximum(cnt, 1)
+                acc_columns.append((key, np.where(cnt > 0, v, np.nan).tolist()))
+        rows = []
+        for i in range(N):
+            r = res["res"][i]
+            n = int(r["searched_steps"])
+            row = {k: 0.0 for k in EPISODE_RESULT_HEADS}
+            row.update(num=i, len=int(r["len"]), discounted_return=float(r["discounted_return"]),
+                       time=elapsed, env_seed=int(r["env_seed"]), slot=int(res["slot"][i]),
+                       slot_order=int(res["slot_order"][i]))
+            row["return"] = float(r["ret"])
+            if n == 0:
+                for k in EPISODE_RESULT_HEADS[5:]:
+                    row[k] = np.nan
+            else:
+                row.update(search_time=search_ms / 1e3 / steps, update_time=upd_ms / 1e3 / steps,
+                           search_depth=int(r["search_depth_sum"]) / n,
+                           num_sims=int(r["num_sims_sum"]) / n, mem_usage=mem,
+                           min_value=float(r["min_value_sum"]) / n,
+                           max_value=float(r["max_value_sum"]) / n)
+            if pop_ids is not None:
+                row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
+            for key, col in acc_columns:
+                row[key] = col[i]
+            if write_row is not None:
+                write_row(row)
+            rows.append(row)
+        return rows
+
+    def episode_queue_slots(self):
+        """The queue entry each slot of a running ``run_episode_queue`` is playing
+        (-1: retired).  ``on_step`` may read it."""
+        return self.engine.episodes_queue_slots()
+
+    def episode_queue_finished(self):
+        """The episodes that ended in the step just played: per slot the queue
+        entry (-1: none) and the episode's final ``pomcp_episode_state``."""
+        return self.engine.episodes_queue_finished()
+
     def _belief_acc_stats(self, belief_acc):
         """``run_episodes``' ``belief_acc`` as the tracker's ``stats_to_track``
         ([] = off), refused as ``BeliefStatTracker`` refuses it."""

@@ -30,11 +30,25 @@ The two routes' ``belief_state_acc`` columns must agree bit for bit.  The record
 is stored under the key ``"belief_acc"`` of the ``--out`` file's record, beside
 the figures already there.
 
+With ``--queue`` it times the episode queue: ``run_episode_queue`` over
+``--rounds`` x trees seeds (a finished tree refilled on the device) against the
+route there was before, that many successive ``run_episodes`` calls over the
+same seeds on one engine, each after one untimed warm-up of its own on a fresh
+engine.  Reported for both: wall time, batch steps, episode steps per second,
+the share of slot-steps that were live (sum(len) / (trees x batch steps)), the
+device time of the update and the search per step, and for the queue that of
+the rank + refill kernels and of k_log_drop (pomcp_episodes_queue_timing).  The
+two routes assign seeds to planners differently, so their rows differ: rates
+are compared, not rows.  Stored under the key ``"queue"`` (``--until
+agent_done``: ``"queue_agent_done"``).
+
 Usage (one GPU process, under its own time limit):
 
     timeout -k 10 900 python tools/batched_episodes_timing.py \
         --out profiles/batched_episodes_timing.json
     timeout -k 10 900 python tools/batched_episodes_timing.py --belief-acc \
+        --out profiles/batched_episodes_timing.json
+    timeout -k 10 300 python tools/batched_episodes_timing.py --queue \
         --out profiles/batched_episodes_timing.json
 """
 import argparse
@@ -155,8 +169,54 @@ def belief_acc_timing(fresh, seeds, max_steps):
     return rec, agree
 
 
+def queue_timing(fresh, seeds, B, until):
+    """The --queue comparison: N = len(seeds) episodes through run_episode_queue
+    and through N / B successive run_episodes calls on one engine."""
+    def route(queue):
+        bp = fresh()
+        try:
+            t0 = time.perf_counter()
+            steps, upd, search, q_ms = 0, 0.0, 0.0, (0.0, 0.0)
+            if queue:
+                rows = bp.run_episode_queue(seeds, until=until)
+                (upd, search, _), steps = bp.engine.episodes_timing()
+                q_ms = bp.engine.episodes_queue_timing()
+            else:
+                rows = []
+                for i in range(0, len(seeds), B):
+                    rows += bp.run_episodes(seeds[i:i + B], until=until)
+                    (u, s, _), n = bp.engine.episodes_timing()
+                    steps, upd, search = steps + n, upd + u, search + s
+            sec = time.perf_counter() - t0
+        finally:
+            bp.close()
+        played = int(sum(r["len"] for r in rows))
+        return {
+            "episodes": len(rows), "wall_s": sec, "batch_steps": steps,
+            "episode_steps_total": played, "episode_steps_per_s": played / sec,
+            "live_share_of_slot_steps": played / (B * steps),
+            "ms_per_batch_step": sec * 1e3 / steps,
+            "update_ms_per_step": upd / steps, "search_ms_per_step": search / steps,
+            "refill_ms_per_step": q_ms[0] / steps, "k_log_drop_ms_per_step": q_ms[1] / steps,
+        }
+
+    route(True)     # untimed warm-up of both routes' kernels and shapes
+    route(False)
+    rec = {"run_episode_queue": route(True), "successive_run_episodes": route(False)}
+    rec["queue_over_successive_steps_per_s"] = (
+        rec["run_episode_queue"]["episode_steps_per_s"] /
+        rec["successive_run_episodes"]["episode_steps_per_s"])
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--queue", action="store_true",
+                    help="time run_episode_queue over --rounds x trees seeds against that many "
+                         "successive run_episodes calls")
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--until", default="all_done", choices=["all_done", "agent_done"],
+                    help="--queue only; agent_done is stored under the key queue_agent_done")
     ap.add_argument("--trees", type=int, default=4096)
     ap.add_argument("--sims", type=int, default=256)
     ap.add_argument("--first-seed", type=int, default=3000)
@@ -182,6 +242,23 @@ def main():
         # must play the same episodes to be compared row by row
         return BatchedPOMCP(model, "0", MCTSConfig(seed=0, num_sims=S, **CFG), B, S,
                             searches=max_steps, reroot=True, device=dev)
+
+    if args.queue:
+        all_seeds = list(range(args.first_seed, args.first_seed + args.rounds * B))
+        q_rec = dict({"env": "Driving-v1", "trees": B, "sims": S, "until": args.until,
+                      "device": torch.cuda.get_device_name(dev)},
+                     **queue_timing(fresh, all_seeds, B, args.until))
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["queue" if args.until == "all_done" else "queue_" + args.until] = q_rec
+        print(json.dumps(q_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0
 
     if args.belief_acc:
         acc_rec, agree = belief_acc_timing(fresh, seeds, max_steps)
