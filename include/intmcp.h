@@ -146,6 +146,79 @@ int intmcp_set_search_policy(intmcp_ctx* ctx, int32_t level, int32_t agent, cons
 /* Synthetic roots (as pomcp_synthetic_obs). */
 int intmcp_synthetic_obs(intmcp_ctx* ctx, uint64_t env_seed_base, uint64_t* obs_keys_out);
 
+/* ---- Batched episodes on the device (ABI 7, additive; csrc/intmcp_episode.hip)
+ * pomcp_episodes_* (pomcp.h) for planner pairs: pair b plays the episode a single
+ * INTMCP keyed (seed, tree_key_base + b) plays in the serial harness with
+ * environment seed env_seeds[b], with nothing per pair on the host.  The records
+ * are pomcp.h's (pomcp_episode_result / _state / _pop_state, pomcp_episode_until,
+ * pomcp_episode_population).
+ *
+ * A pair whose episode is over is parked: its next update action is INTMCP_SKIP
+ * and its root node reads absorbing, so it is neither updated nor searched and
+ * its arenas stop growing while its neighbours play on.  DURING a batch every
+ * getter above shows a parked pair's root as absorbing, with action 0 and no
+ * simulations; intmcp_episodes_results ends the batch and restores the root
+ * node and the header fields of the pair's last real step, after which the
+ * getters read what they read after that step.  Not offered: belief accuracy
+ * and the episode queue of pomcp.h. */
+/* The population of the batches started by the following intmcp_episodes_begin
+ * calls (copied); NULL: the uniform random other agent. */
+int intmcp_episodes_set_population(intmcp_ctx* ctx, const pomcp_episode_population* pop);
+/* intmcp_reset, then every pair's episode starts (as pomcp_episodes_begin:
+ * pow_table[t] = discount ** t, max_steps entries). */
+int intmcp_episodes_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
+                          int32_t max_steps, int32_t until);
+/* One step of every unfinished pair: the update from the device inputs, the
+ * search (num_sims_per_level at every level, INTMCP_BEGIN | INTMCP_FINAL), the
+ * environment's answer and the result row (k_im_episode_step).  live_out: the
+ * pairs still playing.  A pair's error ends the batch's step with the text
+ * intmcp_update / intmcp_search give it.  POMCP_E_STATE after
+ * intmcp_episodes_results. */
+int intmcp_episodes_step(intmcp_ctx* ctx, int32_t num_sims_per_level, int32_t* live_out);
+/* Ends the batch (parked pairs restored, see above), then every pair's row
+ * (host, [pairs]).  May be called again; intmcp_episodes_step may not. */
+int intmcp_episodes_results(intmcp_ctx* ctx, pomcp_episode_result* out);
+/* Every pair's whole record / population record (host, [pairs]). */
+int intmcp_episodes_states(intmcp_ctx* ctx, pomcp_episode_state* out);
+int intmcp_episodes_pop_states(intmcp_ctx* ctx, pomcp_episode_pop_state* out);
+/* Device time (ms, events on the context stream) since intmcp_episodes_begin:
+ * ms[0] updates, ms[1] searches, ms[2] k_im_episode_step + the live count;
+ * *steps = intmcp_episodes_step calls. */
+int intmcp_episodes_timing(intmcp_ctx* ctx, double ms[3], int32_t* steps);
+
+/* What k_im_episode_step reads of a pair: fields of its header and the info
+ * word of its planner's root node (bit 3: absorbing). */
+typedef struct intmcp_episode_root {
+  int32_t last_action, num_sims, search_depth, err;   /* the header's, after this step's search */
+  double min_value, max_value;    /* the planner's MinMaxStats */
+  uint32_t info;                  /* the root node's info word */
+  int32_t pad;
+} intmcp_episode_root;
+/* A pair's side record: the header fields of its last real step (one it played
+ * with a search that did not fail) and, while parked, the root node's info
+ * word as it was. */
+typedef struct intmcp_episode_kept {
+  uint32_t info;
+  int32_t last_action, num_sims, search_depth;
+  int32_t parked;                 /* 1: the root's absorbing bit was set by the park */
+  int32_t pad[3];
+} intmcp_episode_kept;
+/* Host twins of k_im_episode_step / k_im_episode_unpark's per-pair code
+ * (csrc/intmcp_episode.h).  ego: the planning agent; grid, pop, ps as
+ * pomcp_host_episode_step_pop.  *next_action: the pair's next update action --
+ * the ego's action, INTMCP_SKIP for a pair that finished in this step (root->info
+ * then carries the absorbing bit unless the pair failed), or -3 for a pair that
+ * was finished before (nothing changes). */
+int intmcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
+                             intmcp_episode_root* root, intmcp_episode_kept* kept,
+                             const double* pow_table, int32_t max_steps, int32_t until,
+                             const pomcp_episode_population* pop,
+                             const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                             pomcp_episode_step_out* out, int32_t* next_action);
+/* Returns through *changed whether the pair was parked (root restored). */
+int intmcp_host_episode_unpark(intmcp_episode_root* root, intmcp_episode_kept* kept,
+                               int32_t* changed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
 #include "episode_queue.h"
 #include "episode_step.h"
 #include "host_exp.h"
+#include "intmcp_episode.h"
 #include "philox.h"
 #include "pursuit_evasion.h"
 #include "../../include/pomcp.h"
@@ -295,6 +296,49 @@ int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
     build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
     episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
   }
+  return POMCP_OK;
+}
+
+// The per-pair work of k_im_episode_step / k_im_episode_unpark
+// (intmcp_episode.hip) on the host, through the same intmcp_episode.h.
+int intmcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
+                             intmcp_episode_root* root, intmcp_episode_kept* kept,
+                             const double* pow_table, int32_t max_steps, int32_t until,
+                             const pomcp_episode_population* pop,
+                             const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                             pomcp_episode_step_out* out, int32_t* next_action) {
+  if (!episode_env_ok(env_id, grid, ego) || !root || !kept || !pow_table || !st || !out ||
+      !next_action || max_steps < 1 ||
+      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
+    return POMCP_E_INVALID;
+  EpPopTables t;
+  if (pop) {
+    if (!ps || !ep_pop_tables(*pop, env_id == POMCP_ENV_DRIVING ? (int)EpDriving::kA
+                                                                : (int)EpPursuitEvasion::kA, &t) ||
+        ps->policy_index < 0 || ps->policy_index >= t.n)
+      return POMCP_E_INVALID;
+  }
+  const EpPopTables* tp = pop ? &t : nullptr;
+  const int k = pop ? ps->policy_index : -1;
+  int parked = 0;
+  if (env_id == POMCP_ENV_DRIVING) {
+    DrvModel m;
+    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
+    *next_action = im_episode_step<EpDriving>(m, ego, root, kept, pow_table, max_steps, until, tp, k,
+                                              st, out, &parked);
+  } else {
+    PeModel m;
+    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
+    *next_action = im_episode_step<EpPursuitEvasion>(m, ego, root, kept, pow_table, max_steps, until,
+                                                     tp, k, st, out, &parked);
+  }
+  return POMCP_OK;
+}
+
+int intmcp_host_episode_unpark(intmcp_episode_root* root, intmcp_episode_kept* kept,
+                               int32_t* changed) {
+  if (!root || !kept || !changed) return POMCP_E_INVALID;
+  *changed = im_episode_unpark(root, kept);
   return POMCP_OK;
 }
 

@@ -9,6 +9,20 @@ struct intmcp_ctx : HostCtx {
   std::vector<int32_t> host_out;
   std::vector<IHdr> host_hdr;
   intmcp_root_stats* dev_rstats = nullptr;   // device staging of intmcp_get_root_stats
+  // batched episodes (intmcp_episodes_begin / _step): the device records (EpDev
+  // as the POMCP layer's, without root statistics, query states or belief
+  // accuracy) and the pairs' side records, whether a batch exists and whether
+  // it has ended (its parked pairs restored), its steps and the device time of
+  // its phases (events on the stream), the other agents' population
+  EpDev ep{};
+  intmcp_episode_kept* ep_kept = nullptr;   // [B]
+  bool ep_active = false, ep_ended = false;
+  int32_t ep_steps = 0;
+  double ep_ms[3] = {0.0, 0.0, 0.0};
+  hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool ep_pop_set = false;
+  EpPopTables host_pop{};
+  EpPopTables* dev_pop = nullptr;
 };
 
 // intmcp_root_stats of every pair's planner root (the level-1 root; at nesting
@@ -89,6 +103,15 @@ static int im_copy_blocks(intmcp_ctx* ctx, std::vector<char>& out, int pair, int
   return POMCP_OK;
 }
 
+// batched episodes: a pair per lane of 256-lane workgroups (intmcp_episode.hip)
+static unsigned im_episode_blocks(int B) { return (unsigned)((B + kEpThreads - 1) / kEpThreads); }
+
+// f(Env{}) with the context's environment as the episode kernels know it (episode_step.h)
+template <class F>
+static void im_with_episode_env(const intmcp_ctx* ctx, F&& f) {
+  env_dispatch<EpDriving, EpPursuitEvasion>(ctx->cfg.base.env_id, f);
+}
+
 extern "C" {
 
 // ctx == NULL: why the last intmcp_create of this thread failed
@@ -98,6 +121,8 @@ const char* intmcp_last_error(const intmcp_ctx* ctx) { return ctx ? ctx->err.c_s
 void intmcp_destroy(intmcp_ctx* ctx) {
   if (!ctx) return;
   ctx->close();
+  for (hipEvent_t e : ctx->ep_ev)
+    if (e) (void)hipEventDestroy(e);
   delete ctx;
 }
 
@@ -228,6 +253,7 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
 int intmcp_reset(intmcp_ctx* ctx) {
   if (!ctx) return POMCP_E_INVALID;
   PB_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->ep_active = false;   // a batch of episodes ends with its trees
   // node lines and records start zeroed: statistics and inline child slots
   // need no initialising writes (intmcp.hip, kImBlock)
   PB_TRY(ctx, hipMemsetAsync(ctx->ip.nodes, 0, (size_t)ctx->ip.B * ctx->ip.nt * ctx->ip.Nn * kImBlock,
@@ -245,17 +271,11 @@ int intmcp_reset(intmcp_ctx* ctx) {
   return POMCP_OK;
 }
 
-int intmcp_update(intmcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_keys,
-                  int32_t* root_absorbing_out) {
-  if (!ctx || !obs_keys) return POMCP_E_INVALID;
-  PB_TRY(ctx, hipSetDevice(ctx->device));
+// INTMCP.update's kernel for every pair, on the inputs in ip.in_actions /
+// ip.in_obs (intmcp_update uploads them; a batched episode step leaves them
+// there).
+static int im_launch_update(intmcp_ctx* ctx) {
   const int B = ctx->ip.B;
-  std::vector<int32_t> acts((size_t)B, -1);
-  if (actions) std::memcpy(acts.data(), actions, sizeof(int32_t) * (size_t)B);
-  int rc;
-  if ((rc = ctx->upload(ctx->ip.in_actions, acts.data(), (size_t)B)) != POMCP_OK ||
-      (rc = ctx->upload(ctx->ip.in_obs, obs_keys, (size_t)B)) != POMCP_OK)
-    return rc;
   // a wave per pair for few pairs (the drop-in): the update's log scans are
   // shared by the wave's lanes (k_im_update kWave); a lane per pair otherwise
   const bool wave = B <= 1024;
@@ -274,6 +294,21 @@ int intmcp_update(intmcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_k
     });
   });
   PB_TRY(ctx, hipGetLastError());
+  return POMCP_OK;
+}
+
+int intmcp_update(intmcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_keys,
+                  int32_t* root_absorbing_out) {
+  if (!ctx || !obs_keys) return POMCP_E_INVALID;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  const int B = ctx->ip.B;
+  std::vector<int32_t> acts((size_t)B, -1);
+  if (actions) std::memcpy(acts.data(), actions, sizeof(int32_t) * (size_t)B);
+  int rc;
+  if ((rc = ctx->upload(ctx->ip.in_actions, acts.data(), (size_t)B)) != POMCP_OK ||
+      (rc = ctx->upload(ctx->ip.in_obs, obs_keys, (size_t)B)) != POMCP_OK)
+    return rc;
+  if ((rc = im_launch_update(ctx)) != POMCP_OK) return rc;
   if ((rc = ctx->fetch(ctx->host_out.data(), ctx->ip.out, 2 * (size_t)B)) != POMCP_OK) return rc;
   if (root_absorbing_out)
     for (int t = 0; t < B; ++t) root_absorbing_out[t] = ctx->host_out[2 * t];
@@ -331,6 +366,11 @@ static int im_searchN(intmcp_ctx* ctx, const int32_t sims[kImMaxT], int32_t flag
   });
   PB_TRY(ctx, hipGetLastError());
   return actions_out ? im_search_actions(ctx, actions_out) : POMCP_OK;
+}
+
+// intmcp_search's launch alone: num_sims simulations at every level, BEGIN | FINAL
+static int im_launch_search(intmcp_ctx* ctx, int32_t num_sims) {
+  return intmcp_search(ctx, num_sims, nullptr);
 }
 
 int intmcp_search(intmcp_ctx* ctx, int32_t num_sims, int32_t* actions_out) {
@@ -627,6 +667,162 @@ int intmcp_synthetic_obs(intmcp_ctx* ctx, uint64_t env_seed_base, uint64_t* obs_
   PB_TRY(ctx, hipGetLastError());
   if (obs_keys_out) return ctx->fetch(obs_keys_out, ctx->ip.out_obs, (size_t)ctx->ip.B);
   PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
+// ------------------------------------------------------------ batched episodes
+
+int intmcp_episodes_set_population(intmcp_ctx* ctx, const pomcp_episode_population* pop) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!pop) {
+    ctx->ep_pop_set = false;   // from the next intmcp_episodes_begin on
+    return POMCP_OK;
+  }
+  EpPopTables t;
+  if (!ep_pop_tables(*pop, ctx->ip.A, &t))
+    return fail(ctx, POMCP_E_INVALID, "episodes_set_population: 1..8 policies, probabilities >= 0 "
+                                      "with a positive sum");
+  ctx->host_pop = t;
+  ctx->ep_pop_set = true;
+  return POMCP_OK;
+}
+
+int intmcp_episodes_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
+                          int32_t max_steps, int32_t until) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!env_seeds || !pow_table || max_steps < 1 ||
+      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
+    return fail(ctx, POMCP_E_INVALID, "episodes_begin: bad arguments");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  const int B = ctx->ip.B;
+  const size_t nB = (size_t)B;
+  EpDev& ep = ctx->ep;
+  int rc;
+  for (hipEvent_t& e : ctx->ep_ev)
+    if (!e) PB_TRY(ctx, hipEventCreate(&e));
+  if (!ep.out) {   // (the last one allocated: a failed attempt is started over)
+    if ((rc = ctx->alloc(ep.st, nB)) != POMCP_OK || (rc = ctx->alloc(ep.ps, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(ctx->ep_kept, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(ep.env_seeds, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(ep.part, 2 * (size_t)im_episode_blocks(B))) != POMCP_OK)
+      return rc;
+    ep.in_actions = const_cast<int32_t*>(ctx->ip.in_actions);
+    ep.in_obs = const_cast<uint64_t*>(ctx->ip.in_obs);
+    if ((rc = ctx->alloc(ep.out, 2)) != POMCP_OK) return rc;
+  }
+  // (an earlier, shorter table stays allocated until the context goes)
+  if ((ep.pow_table == nullptr || ep.max_steps != max_steps) &&
+      (rc = ctx->alloc(ep.pow_table, (size_t)max_steps)) != POMCP_OK)
+    return rc;
+  ep.max_steps = max_steps;
+  ep.until = until;
+  ep.pop = nullptr;
+  if (ctx->ep_pop_set) {
+    if ((!ctx->dev_pop && (rc = ctx->alloc(ctx->dev_pop, 1)) != POMCP_OK) ||
+        (rc = ctx->upload(ctx->dev_pop, &ctx->host_pop, 1)) != POMCP_OK)
+      return rc;
+    ep.pop = ctx->dev_pop;
+  }
+  if ((rc = intmcp_reset(ctx)) != POMCP_OK) return rc;   // (ends an earlier batch)
+  if ((rc = ctx->upload(ep.env_seeds, env_seeds, nB)) != POMCP_OK ||
+      (rc = ctx->upload(ep.pow_table, pow_table, (size_t)max_steps)) != POMCP_OK)
+    return rc;
+  im_with_episode_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_im_episode_reset<decltype(e)>, dim3(im_episode_blocks(B)), dim3(kEpThreads),
+                       0, ctx->stream, ctx->ip, ep, ctx->ep_kept);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  // the tables were copied from the caller's memory: finish before returning
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->ep_active = true;
+  ctx->ep_ended = false;
+  ctx->ep_steps = 0;
+  ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
+  return POMCP_OK;
+}
+
+int intmcp_episodes_step(intmcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (num_sims < 0 || !live_out) return fail(ctx, POMCP_E_INVALID, "episodes_step: bad arguments");
+  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_step: intmcp_episodes_begin first");
+  if (ctx->ep_ended)
+    return fail(ctx, POMCP_E_STATE, "episodes_step: intmcp_episodes_results ended the batch");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  const int B = ctx->ip.B;
+  int rc;
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[0], ctx->stream));
+  if ((rc = im_launch_update(ctx)) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[1], ctx->stream));
+  if ((rc = im_launch_search(ctx, num_sims)) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[2], ctx->stream));
+  const unsigned nblk = im_episode_blocks(B);
+  im_with_episode_env(ctx, [&](auto e) {
+    hipLaunchKernelGGL(k_im_episode_step<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
+                       ctx->ip, ctx->ep, ctx->ep_kept);
+  });
+  PB_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
+  PB_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
+  int32_t counts[2] = {0, 0};
+  PB_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->ep_steps += 1;
+  for (int k = 0; k < 3; ++k) {
+    float ms = 0.f;
+    PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
+    ctx->ep_ms[k] += (double)ms;
+  }
+  *live_out = counts[0];
+  if (counts[1] != 0) {   // some pair failed: the update's error first, then the search's
+    if ((rc = ctx->fetch(ctx->host_out.data(), ctx->ip.out, 2 * (size_t)B)) != POMCP_OK ||
+        (rc = im_first_error(ctx, "update",
+                             [&](int t) { return ctx->host_out[2 * (size_t)t + 1]; })) != POMCP_OK ||
+        (rc = im_fetch_hdr(ctx)) != POMCP_OK ||
+        (rc = im_first_error(ctx, "search", [&](int t) { return ctx->host_hdr[t].err; })) != POMCP_OK)
+      return rc;
+    return fail(ctx, POMCP_E_STATE, "episodes_step: an episode record reports an error");
+  }
+  return POMCP_OK;
+}
+
+int intmcp_episodes_states(intmcp_ctx* ctx, pomcp_episode_state* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_states: intmcp_episodes_begin first");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, (const pomcp_episode_state*)ctx->ep.st, (size_t)ctx->ip.B);
+}
+
+int intmcp_episodes_results(intmcp_ctx* ctx, pomcp_episode_result* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_results: intmcp_episodes_begin first");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  // the batch ends: the parked pairs' roots and header fields as their last
+  // real steps left them (a later call finds no pair parked)
+  hipLaunchKernelGGL(k_im_episode_unpark, dim3(im_episode_blocks(ctx->ip.B)), dim3(kEpThreads), 0,
+                     ctx->stream, ctx->ip, ctx->ep_kept);
+  PB_TRY(ctx, hipGetLastError());
+  ctx->ep_ended = true;
+  std::vector<pomcp_episode_state> st((size_t)ctx->ip.B);
+  const int rc = intmcp_episodes_states(ctx, st.data());
+  if (rc != POMCP_OK) return rc;
+  for (int t = 0; t < ctx->ip.B; ++t) out[t] = st[t].res;
+  return POMCP_OK;
+}
+
+int intmcp_episodes_pop_states(intmcp_ctx* ctx, pomcp_episode_pop_state* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active)
+    return fail(ctx, POMCP_E_STATE, "episodes_pop_states: intmcp_episodes_begin first");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, (const pomcp_episode_pop_state*)ctx->ep.ps, (size_t)ctx->ip.B);
+}
+
+int intmcp_episodes_timing(intmcp_ctx* ctx, double ms[3], int32_t* steps) {
+  if (!ctx || !ms || !steps) return POMCP_E_INVALID;
+  for (int k = 0; k < 3; ++k) ms[k] = ctx->ep_ms[k];
+  *steps = ctx->ep_steps;
   return POMCP_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "pomcp_search_lds.hip"
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
 #include "intmcp.hip"
+#include "intmcp_episode.hip"   // (after ImParams and pomcp_episode.hip's EpDev)
 #include "../../include/pomcp_debug.h"
 #include "host_ctx.h"
 

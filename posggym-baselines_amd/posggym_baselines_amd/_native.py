@@ -469,8 +469,36 @@ class IntmcpRootStats(C.Structure):
     ]
 
 
+class IntmcpEpisodeRoot(C.Structure):
+    """``intmcp_episode_root`` (include/intmcp.h)."""
+    _fields_ = [
+        ("last_action", C.c_int32),
+        ("num_sims", C.c_int32),
+        ("search_depth", C.c_int32),
+        ("err", C.c_int32),
+        ("min_value", C.c_double),
+        ("max_value", C.c_double),
+        ("info", C.c_uint32),
+        ("pad", C.c_int32),
+    ]
+
+
+class IntmcpEpisodeKept(C.Structure):
+    """``intmcp_episode_kept`` (include/intmcp.h)."""
+    _fields_ = [
+        ("info", C.c_uint32),
+        ("last_action", C.c_int32),
+        ("num_sims", C.c_int32),
+        ("search_depth", C.c_int32),
+        ("parked", C.c_int32),
+        ("pad", C.c_int32 * 3),
+    ]
+
+
 INTMCP_BEGIN, INTMCP_FINAL = 1, 2
 INTMCP_SKIP = -2
+INTMCP_EPISODE_KEEP_INPUT = -3   # intmcp_host_episode_step: the pair was finished before
+INTMCP_ABSORBING_BIT = 1 << 3    # of a node's info word
 
 # numpy views of the diagnostic records (include/intmcp.h)
 INTMCP_NODE_DTYPE = [("parent", "<i4"), ("info", "<u4"), ("visits", "<i4"), ("t", "<i4"),
@@ -502,6 +530,20 @@ INTMCP_SIGNATURES = [
     ("intmcp_synthetic_obs", C.c_int, [_CTX, C.c_uint64, _PU64]),
     ("intmcp_set_search_policy", C.c_int, [_CTX, C.c_int32, C.c_int32, _PD]),
     ("intmcp_debug_phase_timing", C.c_int, [_CTX, C.c_void_p, C.c_int32, _P32]),
+    ("intmcp_episodes_set_population", C.c_int, [_CTX, C.POINTER(PomcpEpisodePopulation)]),
+    ("intmcp_episodes_begin", C.c_int, [_CTX, _PU64, _PD, C.c_int32, C.c_int32]),
+    ("intmcp_episodes_step", C.c_int, [_CTX, C.c_int32, _P32]),
+    ("intmcp_episodes_results", C.c_int, [_CTX, C.POINTER(PomcpEpisodeResult)]),
+    ("intmcp_episodes_states", C.c_int, [_CTX, C.POINTER(PomcpEpisodeState)]),
+    ("intmcp_episodes_pop_states", C.c_int, [_CTX, C.POINTER(PomcpEpisodePopState)]),
+    ("intmcp_episodes_timing", C.c_int, [_CTX, _PD, _P32]),
+    ("intmcp_host_episode_step", C.c_int,
+     [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(IntmcpEpisodeRoot), C.POINTER(IntmcpEpisodeKept),
+      _PD, C.c_int32, C.c_int32, C.POINTER(PomcpEpisodePopulation),
+      C.POINTER(PomcpEpisodePopState), C.POINTER(PomcpEpisodeState),
+      C.POINTER(PomcpEpisodeStepOut), _P32]),
+    ("intmcp_host_episode_unpark", C.c_int,
+     [C.POINTER(IntmcpEpisodeRoot), C.POINTER(IntmcpEpisodeKept), _P32]),
 ]
 
 _lib = None

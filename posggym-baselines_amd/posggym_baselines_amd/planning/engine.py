@@ -276,6 +276,73 @@ class EngineBase:
             "synthetic_obs")
         return out
 
+    def _tree_records(self, name, dtype, ctype, *args):
+        """A structured array of ``dtype`` for every tree, filled by the C
+        function ``<ABI>_<name>(ctx, *args, out)``."""
+        out = np.zeros(self._B, dtype=dtype)
+        self._check(self._fn(name)(self._ctx, *args, out.ctypes.data_as(C.POINTER(ctype))), name)
+        return out
+
+    # ------------------------------------------------- batched episodes
+    # (the calls both ABIs have: <ABI>_episodes_*; each engine has its own
+    # episodes_begin)
+    def episodes_step(self, num_sims):
+        """One step of every unfinished episode (``<ABI>_episodes_step``); returns
+        the number of trees still playing."""
+        live = C.c_int32()
+        self._check(self._fn("episodes_step")(self._ctx, int(num_sims), C.byref(live)),
+                    "episodes_step")
+        return live.value
+
+    def episodes_results(self):
+        """Every tree's ``pomcp_episode_result`` as a structured array."""
+        return self._tree_records("episodes_results", N.EPISODE_RESULT_DTYPE, N.PomcpEpisodeResult)
+
+    def episodes_states(self):
+        """Every tree's whole ``pomcp_episode_state`` (tests and diagnostics)."""
+        return self._tree_records("episodes_states", N.EPISODE_STATE_DTYPE, N.PomcpEpisodeState)
+
+    def episodes_set_population(self, probs=None, mixture_index=None):
+        """The other agents' population of the batches started from now on
+        (``<ABI>_episodes_set_population``): ``probs`` = one action distribution
+        per policy (``get_pi`` in action order), ``mixture_index[k]`` = the index
+        of policy ``k``'s id among the planner's mixture policies or -1 (the
+        default for every policy); ``None``: back to the uniform random agent."""
+        if probs is None:
+            self._check(self._fn("episodes_set_population")(self._ctx, None),
+                        "episodes_set_population")
+            return
+        if not 1 <= len(probs) <= N.POMCP_MAX_TYPE_POLICIES:
+            raise ValueError(f"a population has 1 to {N.POMCP_MAX_TYPE_POLICIES} policies")
+        mix = [-1] * len(probs) if mixture_index is None else [int(j) for j in mixture_index]
+        if len(mix) != len(probs):
+            raise ValueError("one mixture_index per policy")
+        pop = N.PomcpEpisodePopulation()
+        pop.num_policies = len(probs)
+        for k, pi in enumerate(probs):
+            if len(pi) != self.A:
+                raise ValueError(f"policy {k}: {len(pi)} probabilities for {self.A} actions")
+            for a in range(self.A):
+                pop.pi[k][a] = float(pi[a])
+        for k in range(N.POMCP_MAX_TYPE_POLICIES):
+            pop.mixture_index[k] = mix[k] if k < len(mix) else -1
+        self._check(self._fn("episodes_set_population")(self._ctx, C.byref(pop)),
+                    "episodes_set_population")
+
+    def episodes_pop_states(self):
+        """Every tree's ``pomcp_episode_pop_state``: the policy index its episode
+        drew from the population (-1 without one) and that policy's mixture index."""
+        return self._tree_records("episodes_pop_states", N.EPISODE_POP_STATE_DTYPE,
+                                  N.PomcpEpisodePopState)
+
+    def episodes_timing(self):
+        """Device milliseconds since ``episodes_begin`` spent in (updates,
+        searches, the episode step kernels), and the number of steps."""
+        ms = (C.c_double * 3)()
+        n = C.c_int32()
+        self._check(self._fn("episodes_timing")(self._ctx, ms, C.byref(n)), "episodes_timing")
+        return (ms[0], ms[1], ms[2]), n.value
+
 
 class PomcpEngine(EngineBase):
     SELECTION = {"pucb": N.SEL_PUCB, "ucb": N.SEL_UCB, "uniform": N.SEL_UNIFORM}
@@ -335,13 +402,6 @@ class PomcpEngine(EngineBase):
             self._defer_forced = True
 
     # ------------------------------------------------------------------
-    def _tree_records(self, name, dtype, ctype, *args):
-        """A structured array of ``dtype`` for every tree, filled by the C
-        function ``pomcp_<name>(ctx, *args, out)``."""
-        out = np.zeros(self.num_trees, dtype=dtype)
-        self._check(self._fn(name)(self._ctx, *args, out.ctypes.data_as(C.POINTER(ctype))), name)
-        return out
-
     def root_prior(self, tree=0):
         """Type-based: the root's ObsNode.action_probs (num_actions doubles)."""
         out = (C.c_double * self.A)()
@@ -499,60 +559,11 @@ class PomcpEngine(EngineBase):
             self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
             pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_begin")
 
-    def episodes_step(self, num_sims):
-        """One step of every unfinished episode (``pomcp_episodes_step``); returns
-        the number of trees still playing."""
-        live = C.c_int32()
-        self._check(self._lib.pomcp_episodes_step(self._ctx, int(num_sims), C.byref(live)),
-                    "episodes_step")
-        return live.value
-
-    def episodes_results(self):
-        """Every tree's ``pomcp_episode_result`` as a structured array."""
-        return self._tree_records("episodes_results", N.EPISODE_RESULT_DTYPE, N.PomcpEpisodeResult)
-
-    def episodes_states(self):
-        """Every tree's whole ``pomcp_episode_state`` (tests and diagnostics)."""
-        return self._tree_records("episodes_states", N.EPISODE_STATE_DTYPE, N.PomcpEpisodeState)
-
     def episodes_belief_counts(self):
         """``belief_counts`` against the true states the episode kernels wrote on
         the device (``episodes_begin(..., track_states=True)``)."""
         return self._tree_records("episodes_belief_stats", N.BELIEF_COUNTS_DTYPE,
                                   N.PomcpBeliefCounts)
-
-    def episodes_set_population(self, probs=None, mixture_index=None):
-        """The other agents' population of the batches started from now on
-        (``pomcp_episodes_set_population``): ``probs`` = one action distribution
-        per policy (``get_pi`` in action order), ``mixture_index[k]`` = the index
-        of policy ``k``'s id among the planner's mixture policies or -1 (the
-        default for every policy); ``None``: back to the uniform random agent."""
-        if probs is None:
-            self._check(self._lib.pomcp_episodes_set_population(self._ctx, None),
-                        "episodes_set_population")
-            return
-        if not 1 <= len(probs) <= N.POMCP_MAX_TYPE_POLICIES:
-            raise ValueError(f"a population has 1 to {N.POMCP_MAX_TYPE_POLICIES} policies")
-        mix = [-1] * len(probs) if mixture_index is None else [int(j) for j in mixture_index]
-        if len(mix) != len(probs):
-            raise ValueError("one mixture_index per policy")
-        pop = N.PomcpEpisodePopulation()
-        pop.num_policies = len(probs)
-        for k, pi in enumerate(probs):
-            if len(pi) != self.A:
-                raise ValueError(f"policy {k}: {len(pi)} probabilities for {self.A} actions")
-            for a in range(self.A):
-                pop.pi[k][a] = float(pi[a])
-        for k in range(N.POMCP_MAX_TYPE_POLICIES):
-            pop.mixture_index[k] = mix[k] if k < len(mix) else -1
-        self._check(self._lib.pomcp_episodes_set_population(self._ctx, C.byref(pop)),
-                    "episodes_set_population")
-
-    def episodes_pop_states(self):
-        """Every tree's ``pomcp_episode_pop_state``: the policy index its episode
-        drew from the population (-1 without one) and that policy's mixture index."""
-        return self._tree_records("episodes_pop_states", N.EPISODE_POP_STATE_DTYPE,
-                                  N.PomcpEpisodePopState)
 
     def episodes_track_belief_acc(self, on, per_step=False):
         """Accumulate the belief accuracies of every played step on the device
@@ -580,14 +591,6 @@ class PomcpEngine(EngineBase):
         self._check(self._lib.pomcp_episodes_belief_acc_ms(self._ctx, C.byref(ms)),
                     "episodes_belief_acc_ms")
         return ms.value
-
-    def episodes_timing(self):
-        """Device milliseconds since ``episodes_begin`` spent in (updates,
-        searches, the episode step kernels), and the number of steps."""
-        ms = (C.c_double * 3)()
-        n = C.c_int32()
-        self._check(self._lib.pomcp_episodes_timing(self._ctx, ms, C.byref(n)), "episodes_timing")
-        return (ms[0], ms[1], ms[2]), n.value
 
     # ------------------------------------------------- episode queue
     def episodes_queue_begin(self, env_seeds, pow_table, max_steps, until, track_states=False):

@@ -46,6 +46,30 @@ EPISODE_RESULT_HEADS = ["num", "len", "return", "discounted_return", "time"] + \
     PlanningStatTracker.STAT_KEYS
 
 
+def batch_episode_row(num, res, elapsed, search_ms, update_ms, steps, mem):
+    """The ``EPISODE_RESULT_HEADS`` + ``env_seed`` row of one tree (or planner
+    pair) of a batch played on the device, from its ``pomcp_episode_result``
+    ``res`` (``BatchedPOMCP.run_episodes`` documents the columns): the planner
+    columns are means over the ``searched_steps`` (integer sum / n, sequential
+    FP64 sum / n; NaN without such a step), ``search_time`` / ``update_time``
+    the batch's device time per step."""
+    n = int(res["searched_steps"])
+    row = {k: 0.0 for k in EPISODE_RESULT_HEADS}
+    row.update(num=num, len=int(res["len"]), discounted_return=float(res["discounted_return"]),
+               time=elapsed, env_seed=int(res["env_seed"]))
+    row["return"] = float(res["ret"])
+    if n == 0:
+        for k in EPISODE_RESULT_HEADS[5:]:
+            row[k] = math.nan
+    else:
+        row.update(search_time=search_ms / 1e3 / steps, update_time=update_ms / 1e3 / steps,
+                   search_depth=int(res["search_depth_sum"]) / n,
+                   num_sims=int(res["num_sims_sum"]) / n, mem_usage=mem,
+                   min_value=float(res["min_value_sum"]) / n,
+                   max_value=float(res["max_value_sum"]) / n)
+    return row
+
+
 class EpisodeEnvView:
     """What ``BeliefStatTracker`` reads of the reference's ``AgentEnvWrapper``
     (``utils.py:224-266``): ``state``, ``last_obs``, ``last_actions`` (the other

@@ -11,7 +11,8 @@ same device state), ``search_policies``, ``action_spaces``, ``step_limit``,
 ``step_statistics``, ``stat_tracker``, ``root``.
 
 ``BatchedINTMCP`` runs many independent planner pairs in one launch (BASELINE
-config 5: nested trees as a batched launch).
+config 5: nested trees as a batched launch); ``BatchedINTMCP.run_episodes``
+plays one whole episode per pair on the device.
 
 Scope (DESIGN.md "I-NTMCP"): nesting levels 0 to 5, random or
 fixed-distribution search policies (``RandomSearchPolicy`` /
@@ -222,6 +223,20 @@ class IntmcpEngine(EngineBase):
         self._check(self._lib.intmcp_search(self._ctx, int(num_sims),
                                             out.ctypes.data_as(C.POINTER(C.c_int32))), "search")
         return out
+
+    def episodes_begin(self, env_seeds, pow_table, max_steps, until):
+        """Reset every pair and start one episode per pair on the device
+        (``intmcp_episodes_begin``); ``until`` is "agent_done" or "all_done".
+        ``episodes_step`` / ``_results`` / ``_states`` / ``_pop_states`` /
+        ``_set_population`` / ``_timing`` are ``EngineBase``'s."""
+        seeds = np.ascontiguousarray(np.asarray(env_seeds, dtype=np.uint64).reshape(self.num_pairs))
+        pw = np.ascontiguousarray(np.asarray(pow_table, dtype=np.float64))
+        if len(pw) < int(max_steps):
+            raise ValueError("pow_table needs max_steps entries")
+        mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
+        self._check(self._lib.intmcp_episodes_begin(
+            self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+            pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_begin")
 
     def set_search_policy(self, level, agent_index, probs=None):
         """``search_policies[level][agent]``: None (random) or a fixed action
@@ -589,6 +604,9 @@ class BatchedINTMCP:
             step_limit = config.step_limit or model.spec.max_episode_steps
             capacities = plan_intmcp_capacities(config, step_limit, num_sims, searches,
                                                 model.action_spaces[agent_id].n, nesting_level)
+            self._planned_searches = int(searches)
+        else:
+            self._planned_searches = None   # the caller's own capacities: not second-guessed
         self.num_pairs = num_pairs
         self.num_sims = num_sims
         self.engine = IntmcpEngine(model, agent_id, config, num_pairs=num_pairs,
@@ -604,6 +622,112 @@ class BatchedINTMCP:
 
     def search(self, fetch=True):
         return self.engine.search(self.num_sims, fetch=fetch)
+
+    # ------------------------------------------------------------ episodes
+    def run_episodes(self, env_seeds=None, *, until: str = "agent_done", max_steps=None,
+                     other_agents=None, write_row=None, on_step=None):
+        """Play one episode per planner pair, the whole batch in lockstep on the
+        device; returns one result row per pair (``BatchedPOMCP.run_episodes``
+        for I-NTMCP).
+
+        Pair ``b`` plays the episode a single ``INTMCP`` keyed ``(seed,
+        tree_key_base + b)`` plays in the serial harness
+        (``run_planning_episodes``) with environment seed ``env_seeds[b]``
+        (default ``b``): same actions, rewards, length and returns, bit for bit.
+        Every step is one call (``intmcp_episodes_step``: the update from the
+        device inputs, the search with ``num_sims`` simulations per level,
+        ``k_im_episode_step``) and one integer comes back, the number of pairs
+        still playing.  ``until``: "agent_done" or "all_done"; an episode is
+        truncated after ``max_steps`` steps (default and upper limit: the model's
+        ``spec.max_episode_steps``).  The planners' RNG streams are not reseeded
+        between calls: a fresh engine replays the first call.
+
+        A pair's nodes and logs grow with every search (I-NTMCP has no
+        compaction), so its arenas must hold the whole episode: create the
+        engine with ``searches=max_steps`` (explicit ``capacities`` are the
+        caller's).  A pair whose episode is over is parked -- neither updated
+        nor searched, its arenas stop growing -- while its neighbours play on.
+        DURING the batch (``on_step``) the engine's getters show a parked pair's
+        root as absorbing with action 0 and no simulations; when the call
+        returns they read what they read after the pair's last step
+        (``root_stats()``, ``nodes()``, ``root_belief()``, ``support()``).
+
+        Rows: ``BatchedPOMCP.run_episodes``' (``EPISODE_RESULT_HEADS`` +
+        ``env_seed``; the planner columns are means over the steps that reached
+        the planner's statistics, ``time`` / ``search_time`` / ``update_time``
+        the batch's figures), plus ``other_policy_id`` with ``other_agents``: a
+        population of 1 to 8 ``FixedDistributionPolicy`` the other agent of
+        every episode is drawn from, as ``PopulationAgents`` draws it for the
+        serial harness.  ``write_row(row)`` is called per pair at the end,
+        ``on_step(t, self)`` after every step (``episode_states()`` and
+        ``episode_pop_states()`` are the getters for it).
+
+        Not offered: ``belief_acc`` / ``belief_states`` (``BeliefStatTracker``
+        has no parity target for an ``INTMCP``) and the episode queue
+        (``run_episode_queue``: resetting one pair inside a live batch is a
+        separate piece of work).
+        """
+        from posggym_baselines_amd.planning.episodes import batch_episode_row
+        if until not in ("agent_done", "all_done"):
+            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        B = self.num_pairs
+        seeds = list(range(B)) if env_seeds is None else [int(s) for s in env_seeds]
+        if len(seeds) != B:
+            raise ValueError(f"env_seeds has {len(seeds)} entries for {B} pairs")
+        spec = getattr(self.engine.model, "spec", None)
+        limit = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
+        if limit < 1:
+            raise ValueError("run_episodes needs the model's spec.max_episode_steps")
+        max_steps = limit if max_steps is None else int(max_steps)
+        if not 1 <= max_steps <= limit:
+            raise ValueError(f"max_steps must be 1 to the model's max_episode_steps ({limit}), "
+                             f"not {max_steps}")
+        if self._planned_searches is not None and self._planned_searches < max_steps:
+            raise ValueError(
+                f"run_episodes searches up to {max_steps} times per pair and a pair's arenas hold "
+                f"the whole episode: create the engine with BatchedINTMCP(..., searches={max_steps}) "
+                f"(this one was sized with searches={self._planned_searches})")
+        pop_ids = pop_probs = None
+        if other_agents is not None:
+            from posggym_baselines_amd.planning.episodes import check_population
+            other_agents = list(other_agents)
+            pop_probs = check_population(other_agents, self.engine.A)
+            pop_ids = [pol.policy_id for pol in other_agents]
+        gamma = self.engine.config.discount
+        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
+        start = time.time()
+        self.engine.episodes_set_population(pop_probs)
+        self.engine.episodes_begin(seeds, pow_table, max_steps, until)
+        live, t = B, 0
+        while live > 0 and t < max_steps:
+            live = self.engine.episodes_step(self.num_sims)
+            if on_step is not None:
+                on_step(t, self)
+            t += 1
+        res = self.engine.episodes_results()   # (ends the batch: parked pairs restored)
+        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
+        elapsed = time.time() - start
+        mem = psutil.Process().memory_info().rss / 1024**2
+        pops = self.engine.episodes_pop_states() if pop_ids is not None else None
+        rows = []
+        for b in range(B):
+            row = batch_episode_row(b, res[b], elapsed, search_ms, upd_ms, steps, mem)
+            if pops is not None:
+                row["other_policy_id"] = pop_ids[int(pops["policy_index"][b])]
+            if write_row is not None:
+                write_row(row)
+            rows.append(row)
+        return rows
+
+    def episode_states(self):
+        """Every pair's ``pomcp_episode_state`` of the running (or last) batch of
+        episodes as a structured array: the debug getter for ``on_step``."""
+        return self.engine.episodes_states()
+
+    def episode_pop_states(self):
+        """Every pair's ``pomcp_episode_pop_state``: the policy its episode drew
+        from ``other_agents`` (-1 without a population)."""
+        return self.engine.episodes_pop_states()
 
     def close(self):
         self.engine.close()

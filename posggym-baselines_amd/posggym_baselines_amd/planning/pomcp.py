@@ -511,7 +511,7 @@ class BatchedPOMCP:
         carry no policy (``state_belief_only``), and ``policy`` is 0.0 for a
         true policy the planners do not model (the uniform agent included).
         """
-        from posggym_baselines_amd.planning.episodes import EPISODE_RESULT_HEADS
+        from posggym_baselines_amd.planning.episodes import batch_episode_row
         if until not in ("agent_done", "all_done"):
             raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
         B = self.num_trees
@@ -582,21 +582,7 @@ class BatchedPOMCP:
                 acc_columns.append((key, col.tolist()))
         rows = []
         for b in range(B):
-            r = res[b]
-            n = int(r["searched_steps"])
-            row = {k: 0.0 for k in EPISODE_RESULT_HEADS}
-            row.update(num=b, len=int(r["len"]), discounted_return=float(r["discounted_return"]),
-                       time=elapsed, env_seed=int(r["env_seed"]))
-            row["return"] = float(r["ret"])
-            if n == 0:
-                for k in EPISODE_RESULT_HEADS[5:]:
-                    row[k] = np.nan
-            else:
-                row.update(search_time=search_ms / 1e3 / steps, update_time=upd_ms / 1e3 / steps,
-                           search_depth=int(r["search_depth_sum"]) / n,
-                           num_sims=int(r["num_sims_sum"]) / n, mem_usage=mem,
-                           min_value=float(r["min_value_sum"]) / n,
-                           max_value=float(r["max_value_sum"]) / n)
+            row = batch_episode_row(b, res[b], elapsed, search_ms, upd_ms, steps, mem)
             if pops is not None:
                 row["other_policy_id"] = pop_ids[int(pops["policy_index"][b])]
             if acc is not None:
@@ -639,7 +625,7 @@ class BatchedPOMCP:
         records of the episodes that ended in the step just played (their
         slots' ``episode_states()`` are the next episodes' by then).
         """
-        from posggym_baselines_amd.planning.episodes import EPISODE_RESULT_HEADS
+        from posggym_baselines_amd.planning.episodes import batch_episode_row
         if until not in ("agent_done", "all_done"):
             raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
         B = self.num_trees
@@ -699,22 +685,8 @@ class BatchedPOMCP:
                 acc_columns.append((key, np.where(cnt > 0, v, np.nan).tolist()))
         rows = []
         for i in range(N):
-            r = res["res"][i]
-            n = int(r["searched_steps"])
-            row = {k: 0.0 for k in EPISODE_RESULT_HEADS}
-            row.update(num=i, len=int(r["len"]), discounted_return=float(r["discounted_return"]),
-                       time=elapsed, env_seed=int(r["env_seed"]), slot=int(res["slot"][i]),
-                       slot_order=int(res["slot_order"][i]))
-            row["return"] = float(r["ret"])
-            if n == 0:
-                for k in EPISODE_RESULT_HEADS[5:]:
-                    row[k] = np.nan
-            else:
-                row.update(search_time=search_ms / 1e3 / steps, update_time=upd_ms / 1e3 / steps,
-                           search_depth=int(r["search_depth_sum"]) / n,
-                           num_sims=int(r["num_sims_sum"]) / n, mem_usage=mem,
-                           min_value=float(r["min_value_sum"]) / n,
-                           max_value=float(r["max_value_sum"]) / n)
+            row = batch_episode_row(i, res["res"][i], elapsed, search_ms, upd_ms, steps, mem)
+            row.update(slot=int(res["slot"][i]), slot_order=int(res["slot_order"][i]))
             if pop_ids is not None:
                 row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
             for key, col in acc_columns:

@@ -42,6 +42,19 @@ two routes assign seeds to planners differently, so their rows differ: rates
 are compared, not rows.  Stored under the key ``"queue"`` (``--until
 agent_done``: ``"queue_agent_done"``).
 
+With ``--intmcp`` it times ``BatchedINTMCP.run_episodes`` (one
+intmcp_episodes_step call per step) against the host-stepped loop it replaces:
+``engine.update`` (INTMCP_SKIP for a pair whose episode is over or whose root
+is absorbing) + ``engine.search`` per step, with every pair's environment
+stepped on the host through ``DrivingModel.step`` -- that loop goes on searching
+the pairs whose episode is over.  Same pairs and seeds both ways, a fresh engine
+per route sized with ``searches = 50``, one untimed warm-up; the rows (length,
+return bits) are compared on every pair.  Defaults: 2,048 pairs, 64 simulations
+per level, nesting level 1 (18.8 MiB of arenas per pair, 38 GiB in all).
+Reported per step: wall time of both routes and the device time of the update,
+the search and k_im_episode_step + the live count (intmcp_episodes_timing).
+Stored under the key ``"intmcp"``.
+
 Usage (one GPU process, under its own time limit):
 
     timeout -k 10 900 python tools/batched_episodes_timing.py \
@@ -49,6 +62,8 @@ Usage (one GPU process, under its own time limit):
     timeout -k 10 900 python tools/batched_episodes_timing.py --belief-acc \
         --out profiles/batched_episodes_timing.json
     timeout -k 10 300 python tools/batched_episodes_timing.py --queue \
+        --out profiles/batched_episodes_timing.json
+    timeout -k 10 600 python tools/batched_episodes_timing.py --intmcp \
         --out profiles/batched_episodes_timing.json
 """
 import argparse
@@ -209,6 +224,111 @@ def queue_timing(fresh, seeds, B, until):
     return rec
 
 
+def intmcp_host_route(bp, seeds, num_sims, max_steps):
+    """The host-stepped I-NTMCP loop run_episodes replaces; returns
+    (rows [(len, return)], steps run, seconds)."""
+    import numpy as np
+    from posggym_baselines_amd import _native as N
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning.episodes import UniformRandomAgents
+    B = len(seeds)
+    eng = bp.engine
+    models, others, states = [], [], []
+    keys = np.zeros(B, dtype=np.uint64)
+    for b, s in enumerate(seeds):
+        m = DrivingModel(seed=s)
+        o = UniformRandomAgents(m, s)
+        o.reset()
+        st = m.sample_initial_state()
+        keys[b] = m.obs_key(m.sample_initial_obs(st)["0"])
+        models.append(m)
+        others.append(o)
+        states.append(st)
+    t0 = time.perf_counter()
+    eng.reset()
+    last = np.full(B, -1, dtype=np.int32)
+    absorbing = np.zeros(B, dtype=bool)
+    done = np.zeros(B, dtype=bool)
+    lens = np.zeros(B, dtype=np.int64)
+    rets = [0.0] * B
+    steps = 0
+    while not done.all() and steps < max_steps:
+        acts_in = np.where(done | absorbing, N.INTMCP_SKIP, last).astype(np.int32)
+        was_absorbing = absorbing
+        absorbing = eng.update(acts_in, keys)
+        actions = eng.search(num_sims)
+        for b in np.nonzero(~done)[0]:
+            m = models[b]
+            # planner.step: an absorbing root returns the last action (intmcp.py:114-136)
+            a = int(last[b]) if was_absorbing[b] else int(actions[b])
+            ts = m.step(states[b], {"0": a, "1": others[b].act("1")})
+            states[b] = ts.state
+            keys[b] = m.obs_key(ts.observations["0"])
+            last[b] = a
+            rets[b] += ts.rewards["0"]
+            lens[b] += 1
+            done[b] = ts.all_done or lens[b] >= max_steps
+        steps += 1
+    sec = time.perf_counter() - t0
+    return [(int(lens[b]), float(rets[b]).hex()) for b in range(B)], steps, sec
+
+
+def intmcp_timing(args):
+    """The --intmcp comparison; returns (record, rows agree)."""
+    import torch
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning import BatchedINTMCP, MCTSConfig
+    B = args.trees if args.trees is not None else 2048
+    S = args.sims if args.sims is not None else 64
+    model = DrivingModel()
+    max_steps = model.spec.max_episode_steps
+    seeds = list(range(args.first_seed, args.first_seed + B))
+    cfg = MCTSConfig(seed=0, num_sims=S, **dict(CFG, state_belief_only=False))
+
+    def fresh():
+        return BatchedINTMCP(model, "0", cfg, B, S, searches=max_steps, device=args.device,
+                             nesting_level=1)
+
+    bp = fresh()
+    caps = bp.engine.capacities
+    try:
+        bp.run_episodes(seeds, until="all_done")   # warm-up: every kernel and shape of both routes
+    finally:
+        bp.close()
+    bp = fresh()
+    try:
+        t0 = time.perf_counter()
+        rows = bp.run_episodes(seeds, until="all_done")
+        dev_sec = time.perf_counter() - t0
+        (upd_ms, search_ms, step_ms), dev_steps = bp.engine.episodes_timing()
+    finally:
+        bp.close()
+    bp = fresh()
+    try:
+        host_rows, host_steps, host_sec = intmcp_host_route(bp, seeds, S, max_steps)
+    finally:
+        bp.close()
+    agree = [(r["len"], float(r["return"]).hex()) for r in rows] == host_rows
+    dev_ms = dev_sec * 1e3 / dev_steps
+    host_ms = host_sec * 1e3 / host_steps
+    rec = {
+        "env": "Driving-v1", "pairs": B, "sims_per_level": S, "nesting_level": 1,
+        "until": "all_done", "searches": max_steps,
+        "arena_bytes_per_pair": caps.bytes_per_pair(model.action_spaces["0"].n),
+        "device": torch.cuda.get_device_name(args.device),
+        "episode_steps_total": int(sum(r["len"] for r in rows)),
+        "run_episodes_steps": dev_steps, "run_episodes_s": dev_sec,
+        "run_episodes_ms_per_step": dev_ms,
+        "update_ms_per_step": upd_ms / dev_steps, "search_ms_per_step": search_ms / dev_steps,
+        "k_im_episode_step_ms_per_step": step_ms / dev_steps,
+        "host_route_steps": host_steps, "host_route_s": host_sec,
+        "host_route_ms_per_step": host_ms,
+        "host_over_run_episodes": host_ms / dev_ms,
+        "rows_agree": bool(agree),
+    }
+    return rec, agree
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--queue", action="store_true",
@@ -217,8 +337,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--until", default="all_done", choices=["all_done", "agent_done"],
                     help="--queue only; agent_done is stored under the key queue_agent_done")
-    ap.add_argument("--trees", type=int, default=4096)
-    ap.add_argument("--sims", type=int, default=256)
+    ap.add_argument("--intmcp", action="store_true",
+                    help="time BatchedINTMCP.run_episodes against the host-stepped loop "
+                         "(defaults: 2048 pairs, 64 simulations per level)")
+    ap.add_argument("--trees", type=int, default=None, help="default 4096 (--intmcp: 2048 pairs)")
+    ap.add_argument("--sims", type=int, default=None, help="default 256 (--intmcp: 64 per level)")
     ap.add_argument("--first-seed", type=int, default=3000)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default="-", help="JSON record path ('-': stdout only)")
@@ -231,7 +354,20 @@ def main():
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
 
     assert torch.cuda.is_available(), "this measurement needs the GPU"
-    B, S, dev = args.trees, args.sims, args.device
+    if args.intmcp:
+        im_rec, agree = intmcp_timing(args)
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["intmcp"] = im_rec
+        print(json.dumps(im_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0 if agree else 1
+    B, S, dev = args.trees or 4096, args.sims or 256, args.device
     model = DrivingModel()
     max_steps = model.spec.max_episode_steps
     seeds = list(range(args.first_seed, args.first_seed + B))
