@@ -159,8 +159,9 @@ int intmcp_synthetic_obs(intmcp_ctx* ctx, uint64_t env_seed_base, uint64_t* obs_
  * getter above shows a parked pair's root as absorbing, with action 0 and no
  * simulations; intmcp_episodes_results ends the batch and restores the root
  * node and the header fields of the pair's last real step, after which the
- * getters read what they read after that step.  Not offered: belief accuracy
- * and the episode queue of pomcp.h. */
+ * getters read what they read after that step.  The episode queue of pomcp.h
+ * is offered below (intmcp_episodes_queue_begin).  Not offered: belief accuracy
+ * and more than one GPU. */
 /* The population of the batches started by the following intmcp_episodes_begin
  * calls (copied); NULL: the uniform random other agent. */
 int intmcp_episodes_set_population(intmcp_ctx* ctx, const pomcp_episode_population* pop);
@@ -218,6 +219,54 @@ int intmcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
 /* Returns through *changed whether the pair was parked (root restored). */
 int intmcp_host_episode_unpark(intmcp_episode_root* root, intmcp_episode_kept* kept,
                                int32_t* changed);
+
+/* ---- Per-pair reset and the episode queue (ABI 7, additive;
+ * csrc/intmcp_episode_queue.hip) ------------------------------------------
+ * intmcp_reset for the n listed pairs only, on the device: each one's node
+ * blocks (the used prefix of every tree), obs-child maps, arena counters and
+ * header fields are left exactly as intmcp_reset leaves them -- its RNG
+ * counters, seed and tree key carry on, as intmcp_reset carries them -- and no
+ * byte of any other pair changes.  POMCP_E_INVALID for an index out of range or
+ * listed twice; POMCP_E_STATE while a batch of episodes is active (between
+ * intmcp_episodes_begin and intmcp_episodes_results). */
+int intmcp_reset_pairs(intmcp_ctx* ctx, const int32_t* pairs, int32_t n);
+/* The episode queue of pomcp.h for planner pairs: n >= pairs episodes on the
+ * batch's slots, with pomcp.h's assignment rule (slot b starts with entry b;
+ * after each step the slots whose episode finished in it take the entries next,
+ * next + 1, ... in ascending slot order while entries remain; a slot that finds
+ * the queue empty is retired and stays parked).  A refilled slot is reset as
+ * intmcp_reset_pairs resets it, so every episode starts from empty arenas and
+ * the episodes slot b plays are those a single INTMCP keyed (seed,
+ * tree_key_base + b) plays, with reset() between them, in the serial harness.
+ * intmcp_episodes_queue_begin is intmcp_episodes_begin on env_seeds[0 .. pairs),
+ * then queue mode; intmcp_reset and intmcp_episodes_begin end it.  While a queue
+ * is active intmcp_episodes_step also ranks the finished slots, writes their
+ * rows and refills them; live_out counts the unfinished plus the refilled
+ * slots. */
+int intmcp_episodes_queue_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
+                                const double* pow_table, int32_t max_steps, int32_t until);
+/* The rows (host, [n], queue order; acc is zero: no belief accuracy); the row of
+ * an entry that has not finished is zero. */
+int intmcp_episodes_queue_rows(intmcp_ctx* ctx, pomcp_episode_queue_row* out);
+/* The entry each slot is playing (host, [pairs]; -1: retired). */
+int intmcp_episodes_queue_slots(intmcp_ctx* ctx, int32_t* out);
+/* The episodes that ended in the last step (host, [pairs] each):
+ * queue_index_out[b] = the entry that ended in slot b, else -1, and
+ * states_out[b] its final record. */
+int intmcp_episodes_queue_finished(intmcp_ctx* ctx, pomcp_episode_state* states_out,
+                                   int32_t* queue_index_out);
+/* Device time (ms) since intmcp_episodes_queue_begin: ms[0] the rank, list and
+ * refill kernels, ms[1] the arena clear (k_im_clear_pairs); neither is part of
+ * intmcp_episodes_timing's ms[2]. */
+int intmcp_episodes_queue_timing(intmcp_ctx* ctx, double ms[2]);
+/* Host twin of k_im_queue_refill's per-slot decision (csrc/intmcp_episode.h
+ * im_episode_refill).  assign: pomcp_host_queue_assign's decision for the slot.
+ * A new entry (>= 0): *kept is cleared with parked = 0, *next_action = -1 (an
+ * initial update), *refilled = 1.  Retired (-1) or still playing (-2): *kept is
+ * left alone, *next_action = -3 (the update input stays as the step left it),
+ * *refilled = 0. */
+int intmcp_host_episode_refill(int32_t assign, intmcp_episode_kept* kept, int32_t* next_action,
+                               int32_t* refilled);
 
 #ifdef __cplusplus
 }

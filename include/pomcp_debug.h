@@ -39,6 +39,16 @@ int pomcp_debug_set_spin_limit(pomcp_ctx* ctx, int32_t polls);
  * this call on the exact-path draws are counted: intmcp_debug_exact_draws. */
 int intmcp_debug_set_softmax_slack(intmcp_ctx* ctx, float slack);
 int intmcp_debug_exact_draws(intmcp_ctx* ctx, uint64_t* count);
+/* I-NTMCP: what one tree's arenas of one pair hold, over their whole capacity
+ * (tests of intmcp_reset_pairs; slow): out[0] = the node blocks in [0,
+ * max_nodes) with any non-zero byte (line or action records), out[1] = one past
+ * the highest such block (0: none), out[2] = the obs-child map slots that are
+ * not the empty entry. */
+int intmcp_debug_arena_scan(intmcp_ctx* ctx, int32_t pair, int32_t tree, int64_t out[3]);
+/* I-NTMCP episode queue: the bytes the arena clear (k_im_clear_pairs) stored
+ * since intmcp_episodes_queue_begin -- node blocks and obs-child maps of every
+ * refilled slot (tools/batched_episodes_timing.py --intmcp-queue). */
+int intmcp_debug_queue_cleared_bytes(intmcp_ctx* ctx, int64_t* bytes);
 /* k_search's fast UCB / PUCB selection (DESIGN.md §4 "Fast selection") takes
  * the fast scores' leader unless an action with different statistics scores
  * within `rel` of it relative to their magnitudes, and then decides with the

@@ -342,6 +342,14 @@ int intmcp_host_episode_unpark(intmcp_episode_root* root, intmcp_episode_kept* k
   return POMCP_OK;
 }
 
+// k_im_queue_refill's decision per slot (intmcp_episode.h im_episode_refill).
+int intmcp_host_episode_refill(int32_t assign, intmcp_episode_kept* kept, int32_t* next_action,
+                               int32_t* refilled) {
+  if (!kept || !next_action || !refilled || assign < kQueuePlaying) return POMCP_E_INVALID;
+  *refilled = im_episode_refill(assign, kept, next_action);
+  return POMCP_OK;
+}
+
 // The arithmetic k_episode_belief_acc does on a played tree's counts
 // (belief_stats.h bel_accuracy).
 int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_index,

@@ -23,6 +23,21 @@ struct intmcp_ctx : HostCtx {
   bool ep_pop_set = false;
   EpPopTables host_pop{};
   EpPopTables* dev_pop = nullptr;
+  // the per-pair reset (intmcp_reset_pairs, the episode queue): the pairs to
+  // reset and their count, on the device
+  int32_t* rp_list = nullptr;   // [B]
+  int32_t* rp_cnt = nullptr;    // [1]
+  // the episode queue (intmcp_episodes_queue_begin): whether the running batch
+  // has one, its device state and the capacity of its per-entry arrays, the
+  // device time of its kernels ({rank + list + refill, the arena clear}) and
+  // their events
+  bool q_active = false;
+  EpQueueDev q{};
+  int32_t q_cap = 0;
+  double q_ms[2] = {0.0, 0.0};
+  hipEvent_t q_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t* q_cleared = nullptr;   // [B] 16 B words the clear stored for each slot's refills
+  unsigned long long* dbg_scan = nullptr;   // [3] intmcp_debug_arena_scan's counts
 };
 
 // intmcp_root_stats of every pair's planner root (the level-1 root; at nesting
@@ -122,6 +137,8 @@ void intmcp_destroy(intmcp_ctx* ctx) {
   if (!ctx) return;
   ctx->close();
   for (hipEvent_t e : ctx->ep_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : ctx->q_ev)
     if (e) (void)hipEventDestroy(e);
   delete ctx;
 }
@@ -254,6 +271,7 @@ int intmcp_reset(intmcp_ctx* ctx) {
   if (!ctx) return POMCP_E_INVALID;
   PB_TRY(ctx, hipSetDevice(ctx->device));
   ctx->ep_active = false;   // a batch of episodes ends with its trees
+  ctx->q_active = false;    // and its queue
   // node lines and records start zeroed: statistics and inline child slots
   // need no initialising writes (intmcp.hip, kImBlock)
   PB_TRY(ctx, hipMemsetAsync(ctx->ip.nodes, 0, (size_t)ctx->ip.B * ctx->ip.nt * ctx->ip.Nn * kImBlock,
@@ -761,12 +779,40 @@ int intmcp_episodes_step(intmcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
                        ctx->ip, ctx->ep, ctx->ep_kept);
   });
   PB_TRY(ctx, hipGetLastError());
+  if (ctx->q_active) {
+    // the queue: the finished slots ranked, the refilled ones listed, their
+    // arenas cleared (while the headers still hold the old episodes' node
+    // counts), then their rows written, their headers reset and their new
+    // episodes started
+    ctx->q.step = ctx->ep_steps;
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_queue_rank, dim3(1), dim3(kRankThreads), 0, ctx->stream, ctx->ep, ctx->q, B);
+    PB_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_im_queue_list, dim3(nblk), dim3(kEpThreads), 0, ctx->stream, ctx->q,
+                       ctx->rp_list, B);
+    PB_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[1], ctx->stream));
+    hipLaunchKernelGGL(k_im_clear_pairs, dim3(kImClearGrid), dim3(kImClearThreads), 0, ctx->stream,
+                       ctx->ip, (const int32_t*)ctx->rp_list, (const int32_t*)(ctx->q.state + 1));
+    PB_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[2], ctx->stream));
+    im_with_episode_env(ctx, [&](auto e) {
+      hipLaunchKernelGGL(k_im_queue_refill<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
+                         ctx->ip, ctx->ep, ctx->q, ctx->ep_kept, ctx->q_cleared);
+    });
+    PB_TRY(ctx, hipGetLastError());
+    PB_TRY(ctx, hipEventRecord(ctx->q_ev[3], ctx->stream));
+  }
   hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
   PB_TRY(ctx, hipGetLastError());
   PB_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
   int32_t counts[2] = {0, 0};
   PB_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
                              ctx->stream));
+  int32_t qstate[2] = {0, 0};   // {next, slots refilled this step}
+  if (ctx->q_active)
+    PB_TRY(ctx, hipMemcpyAsync(qstate, ctx->q.state, sizeof(qstate), hipMemcpyDeviceToHost,
+                               ctx->stream));
   PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->ep_steps += 1;
   for (int k = 0; k < 3; ++k) {
@@ -774,7 +820,15 @@ int intmcp_episodes_step(intmcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
     ctx->ep_ms[k] += (double)ms;
   }
-  *live_out = counts[0];
+  if (ctx->q_active) {   // their own figures, not a part of slot 2
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0.f;
+      PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->q_ev[k], ctx->q_ev[k + 1]));
+      ctx->q_ms[k == 1 ? 1 : 0] += (double)ms;
+      ctx->ep_ms[2] -= (double)ms;
+    }
+  }
+  *live_out = counts[0] + qstate[1];   // (a refilled slot plays on)
   if (counts[1] != 0) {   // some pair failed: the update's error first, then the search's
     if ((rc = ctx->fetch(ctx->host_out.data(), ctx->ip.out, 2 * (size_t)B)) != POMCP_OK ||
         (rc = im_first_error(ctx, "update",
@@ -823,6 +877,169 @@ int intmcp_episodes_timing(intmcp_ctx* ctx, double ms[3], int32_t* steps) {
   if (!ctx || !ms || !steps) return POMCP_E_INVALID;
   for (int k = 0; k < 3; ++k) ms[k] = ctx->ep_ms[k];
   *steps = ctx->ep_steps;
+  return POMCP_OK;
+}
+
+// ------------------------------------------- per-pair reset, the episode queue
+
+// the device list of the pairs to reset and its count
+static int im_ensure_reset_list(intmcp_ctx* ctx) {
+  if (ctx->rp_cnt) return POMCP_OK;   // (the last one allocated)
+  int rc = ctx->alloc(ctx->rp_list, (size_t)ctx->ip.B);
+  return rc != POMCP_OK ? rc : ctx->alloc(ctx->rp_cnt, 1);
+}
+
+int intmcp_reset_pairs(intmcp_ctx* ctx, const int32_t* pairs, int32_t n) {
+  if (!ctx) return POMCP_E_INVALID;
+  const int B = ctx->ip.B;
+  if (n < 0 || n > B || (n > 0 && !pairs))
+    return fail(ctx, POMCP_E_INVALID, "reset_pairs: 0 to num_pairs indices");
+  std::vector<char> seen((size_t)B, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (pairs[i] < 0 || pairs[i] >= B || seen[(size_t)pairs[i]])
+      return fail(ctx, POMCP_E_INVALID, "reset_pairs: index " + std::to_string(pairs[i]) +
+                                        (pairs[i] < 0 || pairs[i] >= B ? " out of range" : " twice"));
+    seen[(size_t)pairs[i]] = 1;
+  }
+  if (ctx->ep_active && !ctx->ep_ended)
+    return fail(ctx, POMCP_E_STATE, "reset_pairs: a batch of episodes is active");
+  if (n == 0) return POMCP_OK;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = im_ensure_reset_list(ctx)) != POMCP_OK ||
+      (rc = ctx->upload((const int32_t*)ctx->rp_list, pairs, (size_t)n)) != POMCP_OK ||
+      (rc = ctx->upload((const int32_t*)ctx->rp_cnt, &n, 1)) != POMCP_OK)
+    return rc;
+  // the clear reads the node counts the header reset overwrites: in this order
+  hipLaunchKernelGGL(k_im_clear_pairs, dim3(kImClearGrid), dim3(kImClearThreads), 0, ctx->stream,
+                     ctx->ip, (const int32_t*)ctx->rp_list, (const int32_t*)ctx->rp_cnt);
+  PB_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_im_reset_pairs, dim3(im_blocks(B)), dim3(64), 0, ctx->stream, ctx->ip,
+                     (const int32_t*)ctx->rp_list, (const int32_t*)ctx->rp_cnt);
+  PB_TRY(ctx, hipGetLastError());
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (`pairs` and `n` are the caller's memory)
+  return POMCP_OK;
+}
+
+int intmcp_episodes_queue_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
+                                const double* pow_table, int32_t max_steps, int32_t until) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!env_seeds || n < ctx->ip.B)
+    return fail(ctx, POMCP_E_INVALID, "episodes_queue_begin: the queue needs at least num_pairs "
+                                      "environment seeds");
+  int rc = intmcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);
+  if (rc != POMCP_OK) return rc;
+  const int B = ctx->ip.B;
+  const size_t nB = (size_t)B;
+  EpQueueDev& q = ctx->q;
+  for (hipEvent_t& e : ctx->q_ev)
+    if (!e) PB_TRY(ctx, hipEventCreate(&e));
+  if ((rc = im_ensure_reset_list(ctx)) != POMCP_OK) return rc;
+  if (!q.fin_q) {   // (the last one allocated)
+    if ((rc = ctx->alloc(q.slot_q, nB)) != POMCP_OK || (rc = ctx->alloc(q.slot_ord, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(q.slot_start, nB)) != POMCP_OK || (rc = ctx->alloc(q.assign, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(q.state, 2)) != POMCP_OK || (rc = ctx->alloc(q.fin, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(ctx->q_cleared, nB)) != POMCP_OK ||
+        (rc = ctx->alloc(q.fin_q, nB)) != POMCP_OK)
+      return rc;
+  }
+  if (n > ctx->q_cap) {   // (an earlier, shorter queue stays allocated until the context goes)
+    ctx->q_cap = 0;
+    if ((rc = ctx->alloc(q.seeds, (size_t)n)) != POMCP_OK ||
+        (rc = ctx->alloc(q.rows, (size_t)n)) != POMCP_OK)
+      return rc;
+    ctx->q_cap = n;
+  }
+  q.drop = nullptr;   // (no shared logs: nothing to drop)
+  q.acc_in = nullptr;
+  q.acc = nullptr;
+  q.n = n;
+  q.step = 0;
+  std::vector<int32_t> iota(nB), minus(nB, -1);
+  for (int b = 0; b < B; ++b) iota[(size_t)b] = b;
+  const int32_t state[2] = {B, 0};
+  if ((rc = ctx->upload(q.seeds, env_seeds, (size_t)n)) != POMCP_OK ||
+      (rc = ctx->upload((const int32_t*)q.slot_q, iota.data(), nB)) != POMCP_OK ||
+      (rc = ctx->upload((const int32_t*)q.fin_q, minus.data(), nB)) != POMCP_OK ||
+      (rc = ctx->upload((const int32_t*)q.state, state, 2)) != POMCP_OK)
+    return rc;
+  PB_TRY(ctx, hipMemsetAsync(q.slot_ord, 0, sizeof(int32_t) * nB, ctx->stream));
+  PB_TRY(ctx, hipMemsetAsync(q.slot_start, 0, sizeof(int32_t) * nB, ctx->stream));
+  PB_TRY(ctx, hipMemsetAsync(q.rows, 0, sizeof(pomcp_episode_queue_row) * (size_t)n, ctx->stream));
+  PB_TRY(ctx, hipMemsetAsync(ctx->q_cleared, 0, sizeof(int64_t) * nB, ctx->stream));
+  // (copied from the caller's and local memory: finish before returning)
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->q_ms[0] = ctx->q_ms[1] = 0.0;
+  ctx->q_active = true;
+  return POMCP_OK;
+}
+
+static int im_queue_ready(intmcp_ctx* ctx, const char* what) {
+  if (!ctx->ep_active || !ctx->q_active)
+    return fail(ctx, POMCP_E_STATE, std::string(what) + ": intmcp_episodes_queue_begin first");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return POMCP_OK;
+}
+
+int intmcp_episodes_queue_rows(intmcp_ctx* ctx, pomcp_episode_queue_row* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  const int rc = im_queue_ready(ctx, "episodes_queue_rows");
+  return rc != POMCP_OK ? rc : ctx->fetch(out, (const pomcp_episode_queue_row*)ctx->q.rows,
+                                          (size_t)ctx->q.n);
+}
+
+int intmcp_episodes_queue_slots(intmcp_ctx* ctx, int32_t* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  const int rc = im_queue_ready(ctx, "episodes_queue_slots");
+  return rc != POMCP_OK ? rc : ctx->fetch(out, (const int32_t*)ctx->q.slot_q, (size_t)ctx->ip.B);
+}
+
+int intmcp_episodes_queue_finished(intmcp_ctx* ctx, pomcp_episode_state* states_out,
+                                   int32_t* queue_index_out) {
+  if (!ctx || !states_out || !queue_index_out) return POMCP_E_INVALID;
+  int rc = im_queue_ready(ctx, "episodes_queue_finished");
+  if (rc != POMCP_OK) return rc;
+  if ((rc = ctx->fetch(queue_index_out, (const int32_t*)ctx->q.fin_q, (size_t)ctx->ip.B)) != POMCP_OK)
+    return rc;
+  return ctx->fetch(states_out, (const pomcp_episode_state*)ctx->q.fin, (size_t)ctx->ip.B);
+}
+
+int intmcp_episodes_queue_timing(intmcp_ctx* ctx, double ms[2]) {
+  if (!ctx || !ms) return POMCP_E_INVALID;
+  ms[0] = ctx->q_ms[0];
+  ms[1] = ctx->q_ms[1];
+  return POMCP_OK;
+}
+
+// Debug (measurement): the bytes k_im_clear_pairs stored since
+// intmcp_episodes_queue_begin, from the per-slot sums k_im_queue_refill keeps.
+int intmcp_debug_queue_cleared_bytes(intmcp_ctx* ctx, int64_t* bytes) {
+  if (!ctx || !bytes) return POMCP_E_INVALID;
+  const int rc0 = im_queue_ready(ctx, "debug_queue_cleared_bytes");
+  if (rc0 != POMCP_OK) return rc0;
+  std::vector<int64_t> words((size_t)ctx->ip.B);
+  const int rc = ctx->fetch(words.data(), (const int64_t*)ctx->q_cleared, words.size());
+  if (rc != POMCP_OK) return rc;
+  int64_t sum = 0;
+  for (int64_t w : words) sum += w;
+  *bytes = 16 * sum;
+  return POMCP_OK;
+}
+
+// Debug (tests): what one tree's node arena and obs-child map hold, scanned
+// over their whole capacity by one workgroup.
+int intmcp_debug_arena_scan(intmcp_ctx* ctx, int32_t pair, int32_t tree, int64_t out[3]) {
+  if (!ctx || !out || pair < 0 || pair >= ctx->ip.B || tree < 0 || tree >= ctx->ip.nt)
+    return POMCP_E_INVALID;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if (!ctx->dbg_scan && (rc = ctx->alloc(ctx->dbg_scan, 3)) != POMCP_OK) return rc;
+  hipLaunchKernelGGL(k_im_arena_scan, dim3(1), dim3(256), 0, ctx->stream, ctx->ip, (int)pair,
+                     (int)tree, ctx->dbg_scan);
+  PB_TRY(ctx, hipGetLastError());
+  unsigned long long got[3] = {0ull, 0ull, 0ull};
+  if ((rc = ctx->fetch(got, (const unsigned long long*)ctx->dbg_scan, 3)) != POMCP_OK) return rc;
+  for (int k = 0; k < 3; ++k) out[k] = (int64_t)got[k];
   return POMCP_OK;
 }
 

@@ -1,9 +1,11 @@
 // One I-NTMCP planner pair's episode, per step: what the step reads of the
 // pair (intmcp_episode_root, from its header and root node), which step keeps
 // the header's search fields, how a finished pair is parked and how it is
-// restored.  One implementation for the device kernels (k_im_episode_step /
-// k_im_episode_unpark, intmcp_episode.hip) and their host twins
-// (intmcp_host_episode_step / intmcp_host_episode_unpark, host_api.cpp), so the
+// restored, and what the episode queue's refill does to a slot.  One
+// implementation for the device kernels (k_im_episode_step /
+// k_im_episode_unpark, intmcp_episode.hip; k_im_queue_refill,
+// intmcp_episode_queue.hip) and their host twins (intmcp_host_episode_step /
+// intmcp_host_episode_unpark / intmcp_host_episode_refill, host_api.cpp), so the
 // CPU suite runs the code the kernels run.  The environment side is
 // episode_step.h's episode_step, engine-independent.  Plain C++: no HIP
 // dependency.
@@ -98,6 +100,31 @@ PB_HD int im_episode_unpark(intmcp_episode_root* root, intmcp_episode_kept* kept
   root->num_sims = kept->num_sims;
   root->search_depth = kept->search_depth;
   kept->parked = 0;
+  return 1;
+}
+
+// The episode queue (intmcp_episodes_queue_begin): what the end of a step does
+// to slot b's side record and next update action, given the queue's decision
+// for it (episode_queue.h queue_assign).  A new entry (assign >= 0): the slot
+// finished in this very step, so im_episode_step has just parked it; the side
+// record is cleared with parked = 0 (the unpark at the end of the batch must
+// not write the old episode's info word into the new episode's root) and the
+// next update is an initial one (action -1).  The absorbing bit the park set
+// goes with the node it sits in: the per-pair reset zeroes the pair's node
+// blocks and writes a fresh node 0.  Retired (kQueueRetire) or still playing
+// (kQueuePlaying): nothing changes, the next action stays as im_episode_step
+// left it (kImEpKeepInput).  Returns 1 for a new entry.
+PB_HD int im_episode_refill(int32_t assign, intmcp_episode_kept* kept, int32_t* next_action) {
+  if (assign < 0) {
+    *next_action = kImEpKeepInput;
+    return 0;
+  }
+  kept->info = 0u;
+  kept->last_action = -1;
+  kept->num_sims = kept->search_depth = 0;
+  kept->parked = 0;
+  kept->pad[0] = kept->pad[1] = kept->pad[2] = 0;
+  *next_action = -1;
   return 1;
 }
 

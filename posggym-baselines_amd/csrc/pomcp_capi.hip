@@ -28,6 +28,7 @@
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
 #include "intmcp.hip"
 #include "intmcp_episode.hip"   // (after ImParams and pomcp_episode.hip's EpDev)
+#include "intmcp_episode_queue.hip"   // (after pomcp_episode_queue.hip's EpQueueDev)
 #include "../../include/pomcp_debug.h"
 #include "host_ctx.h"
 

@@ -425,6 +425,8 @@ DEBUG_SIGNATURES = [
     ("pomcp_debug_log_drop", C.c_int, [C.c_void_p, _PU64]),
     ("intmcp_debug_set_softmax_slack", C.c_int, [C.c_void_p, C.c_float]),
     ("intmcp_debug_exact_draws", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("intmcp_debug_arena_scan", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("intmcp_debug_queue_cleared_bytes", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
 ]
 
 
@@ -544,6 +546,13 @@ INTMCP_SIGNATURES = [
       C.POINTER(PomcpEpisodeStepOut), _P32]),
     ("intmcp_host_episode_unpark", C.c_int,
      [C.POINTER(IntmcpEpisodeRoot), C.POINTER(IntmcpEpisodeKept), _P32]),
+    ("intmcp_reset_pairs", C.c_int, [_CTX, _P32, C.c_int32]),
+    ("intmcp_episodes_queue_begin", C.c_int, [_CTX, _PU64, C.c_int32, _PD, C.c_int32, C.c_int32]),
+    ("intmcp_episodes_queue_rows", C.c_int, [_CTX, C.POINTER(PomcpEpisodeQueueRow)]),
+    ("intmcp_episodes_queue_slots", C.c_int, [_CTX, _P32]),
+    ("intmcp_episodes_queue_finished", C.c_int, [_CTX, C.POINTER(PomcpEpisodeState), _P32]),
+    ("intmcp_episodes_queue_timing", C.c_int, [_CTX, _PD]),
+    ("intmcp_host_episode_refill", C.c_int, [C.c_int32, C.POINTER(IntmcpEpisodeKept), _P32, _P32]),
 ]
 
 _lib = None

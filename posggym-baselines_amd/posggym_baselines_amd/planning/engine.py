@@ -343,6 +343,41 @@ class EngineBase:
         self._check(self._fn("episodes_timing")(self._ctx, ms, C.byref(n)), "episodes_timing")
         return (ms[0], ms[1], ms[2]), n.value
 
+    # ------------------------------------------------- episode queue
+    # (each engine has its own episodes_queue_begin, which sets _queue_len)
+    def episodes_queue_rows(self):
+        """Every queue entry's ``pomcp_episode_queue_row``, in queue order (zero
+        for an entry that has not finished)."""
+        n = getattr(self, "_queue_len", 0)   # (0: no queue was begun; the call says so)
+        out = np.zeros(max(n, 1), dtype=N.EPISODE_QUEUE_ROW_DTYPE)
+        self._check(self._fn("episodes_queue_rows")(
+            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeQueueRow))), "episodes_queue_rows")
+        return out[:n]
+
+    def episodes_queue_slots(self):
+        """The queue entry each tree is playing (-1: retired)."""
+        out = np.zeros(self._B, dtype=np.int32)
+        self._check(self._fn("episodes_queue_slots")(
+            self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_slots")
+        return out
+
+    def episodes_queue_finished(self):
+        """The episodes that ended in the last step: per tree the queue entry
+        (-1: none) and its final ``pomcp_episode_state``."""
+        idx = np.zeros(self._B, dtype=np.int32)
+        st = np.zeros(self._B, dtype=N.EPISODE_STATE_DTYPE)
+        self._check(self._fn("episodes_queue_finished")(
+            self._ctx, st.ctypes.data_as(C.POINTER(N.PomcpEpisodeState)),
+            idx.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_finished")
+        return idx, st
+
+    def episodes_queue_timing(self):
+        """Device milliseconds since ``episodes_queue_begin`` spent in (the rank and
+        refill kernels, ``k_log_drop`` / the I-NTMCP arena clear)."""
+        ms = (C.c_double * 2)()
+        self._check(self._fn("episodes_queue_timing")(self._ctx, ms), "episodes_queue_timing")
+        return ms[0], ms[1]
+
 
 class PomcpEngine(EngineBase):
     SELECTION = {"pucb": N.SEL_PUCB, "ucb": N.SEL_UCB, "uniform": N.SEL_UNIFORM}
@@ -610,39 +645,6 @@ class PomcpEngine(EngineBase):
             self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), len(seeds),
             pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_queue_begin")
         self._queue_len = len(seeds)
-
-    def episodes_queue_rows(self):
-        """Every queue entry's ``pomcp_episode_queue_row``, in queue order (zero
-        for an entry that has not finished)."""
-        n = getattr(self, "_queue_len", 0)   # (0: no queue was begun; the call says so)
-        out = np.zeros(max(n, 1), dtype=N.EPISODE_QUEUE_ROW_DTYPE)
-        self._check(self._lib.pomcp_episodes_queue_rows(
-            self._ctx, out.ctypes.data_as(C.POINTER(N.PomcpEpisodeQueueRow))), "episodes_queue_rows")
-        return out[:n]
-
-    def episodes_queue_slots(self):
-        """The queue entry each tree is playing (-1: retired)."""
-        out = np.zeros(self.num_trees, dtype=np.int32)
-        self._check(self._lib.pomcp_episodes_queue_slots(
-            self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_slots")
-        return out
-
-    def episodes_queue_finished(self):
-        """The episodes that ended in the last step: per tree the queue entry
-        (-1: none) and its final ``pomcp_episode_state``."""
-        idx = np.zeros(self.num_trees, dtype=np.int32)
-        st = np.zeros(self.num_trees, dtype=N.EPISODE_STATE_DTYPE)
-        self._check(self._lib.pomcp_episodes_queue_finished(
-            self._ctx, st.ctypes.data_as(C.POINTER(N.PomcpEpisodeState)),
-            idx.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_finished")
-        return idx, st
-
-    def episodes_queue_timing(self):
-        """Device milliseconds since ``episodes_queue_begin`` spent in (the rank and
-        refill kernels, ``k_log_drop``)."""
-        ms = (C.c_double * 2)()
-        self._check(self._lib.pomcp_episodes_queue_timing(self._ctx, ms), "episodes_queue_timing")
-        return ms[0], ms[1]
 
     def debug_wave_log(self, wave):
         """One search wave's shared particle log in record order

@@ -12,7 +12,9 @@ same device state), ``search_policies``, ``action_spaces``, ``step_limit``,
 
 ``BatchedINTMCP`` runs many independent planner pairs in one launch (BASELINE
 config 5: nested trees as a batched launch); ``BatchedINTMCP.run_episodes``
-plays one whole episode per pair on the device.
+plays one whole episode per pair on the device and
+``BatchedINTMCP.run_episode_queue`` more episodes than pairs, a finished pair
+reset and refilled on the device (§17).
 
 Scope (DESIGN.md "I-NTMCP"): nesting levels 0 to 5, random or
 fixed-distribution search policies (``RandomSearchPolicy`` /
@@ -237,6 +239,49 @@ class IntmcpEngine(EngineBase):
         self._check(self._lib.intmcp_episodes_begin(
             self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
             pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_begin")
+
+    def episodes_queue_begin(self, env_seeds, pow_table, max_steps, until):
+        """``episodes_begin`` on the first ``num_pairs`` seeds, then queue mode
+        (``intmcp_episodes_queue_begin``): a pair whose episode ends is reset on
+        the device and takes the next of ``env_seeds`` (at least ``num_pairs``).
+        The getters (``episodes_queue_rows`` / ``_slots`` / ``_finished`` /
+        ``_timing``) are ``EngineBase``'s."""
+        seeds = np.ascontiguousarray(np.asarray(env_seeds, dtype=np.uint64).reshape(-1))
+        if len(seeds) < self.num_pairs:
+            raise ValueError(f"an episode queue needs at least {self.num_pairs} seeds")
+        pw = np.ascontiguousarray(np.asarray(pow_table, dtype=np.float64))
+        if len(pw) < int(max_steps):
+            raise ValueError("pow_table needs max_steps entries")
+        mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
+        self._check(self._lib.intmcp_episodes_queue_begin(
+            self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), len(seeds),
+            pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_queue_begin")
+        self._queue_len = len(seeds)
+
+    def reset_pairs(self, pairs):
+        """``reset()`` for the listed pairs only, on the device
+        (``intmcp_reset_pairs``): their arenas and headers as a reset leaves
+        them, their RNG streams carried on, every other pair untouched."""
+        idx = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.int32).reshape(-1))
+        self._check(self._lib.intmcp_reset_pairs(
+            self._ctx, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx)), "reset_pairs")
+
+    def debug_arena_scan(self, pair=0, tree=0):
+        """(node blocks with a non-zero byte, one past the highest, occupied
+        obs-child map slots) over one tree's whole arenas
+        (``intmcp_debug_arena_scan``; tests)."""
+        out = (C.c_int64 * 3)()
+        self._check(self._lib.intmcp_debug_arena_scan(self._ctx, int(pair), int(tree), out),
+                    "debug_arena_scan")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def debug_queue_cleared_bytes(self):
+        """Bytes the arena clear stored since ``episodes_queue_begin``
+        (``intmcp_debug_queue_cleared_bytes``; measurements)."""
+        out = C.c_int64()
+        self._check(self._lib.intmcp_debug_queue_cleared_bytes(self._ctx, C.byref(out)),
+                    "debug_queue_cleared_bytes")
+        return int(out.value)
 
     def set_search_policy(self, level, agent_index, probs=None):
         """``search_policies[level][agent]``: None (random) or a fixed action
@@ -624,6 +669,32 @@ class BatchedINTMCP:
         return self.engine.search(self.num_sims, fetch=fetch)
 
     # ------------------------------------------------------------ episodes
+    def _episode_guards(self, what, until, max_steps, other_agents):
+        """What ``run_episodes`` and ``run_episode_queue`` check before anything is
+        launched; returns (max_steps, the population's ids, its distributions)."""
+        if until not in ("agent_done", "all_done"):
+            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        spec = getattr(self.engine.model, "spec", None)
+        limit = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
+        if limit < 1:
+            raise ValueError(f"{what} needs the model's spec.max_episode_steps")
+        max_steps = limit if max_steps is None else int(max_steps)
+        if not 1 <= max_steps <= limit:
+            raise ValueError(f"max_steps must be 1 to the model's max_episode_steps ({limit}), "
+                             f"not {max_steps}")
+        if self._planned_searches is not None and self._planned_searches < max_steps:
+            raise ValueError(
+                f"{what} searches up to {max_steps} times per episode and a pair's arenas hold "
+                f"the whole episode: create the engine with BatchedINTMCP(..., searches={max_steps}) "
+                f"(this one was sized with searches={self._planned_searches})")
+        pop_ids = pop_probs = None
+        if other_agents is not None:
+            from posggym_baselines_amd.planning.episodes import check_population
+            other_agents = list(other_agents)
+            pop_probs = check_population(other_agents, self.engine.A)
+            pop_ids = [pol.policy_id for pol in other_agents]
+        return max_steps, pop_ids, pop_probs
+
     def run_episodes(self, env_seeds=None, *, until: str = "agent_done", max_steps=None,
                      other_agents=None, write_row=None, on_step=None):
         """Play one episode per planner pair, the whole batch in lockstep on the
@@ -662,37 +733,17 @@ class BatchedINTMCP:
         ``on_step(t, self)`` after every step (``episode_states()`` and
         ``episode_pop_states()`` are the getters for it).
 
-        Not offered: ``belief_acc`` / ``belief_states`` (``BeliefStatTracker``
-        has no parity target for an ``INTMCP``) and the episode queue
-        (``run_episode_queue``: resetting one pair inside a live batch is a
-        separate piece of work).
+        More episodes than pairs: ``run_episode_queue``.  Not offered:
+        ``belief_acc`` / ``belief_states`` (``BeliefStatTracker`` has no parity
+        target for an ``INTMCP``) and more than one GPU.
         """
         from posggym_baselines_amd.planning.episodes import batch_episode_row
-        if until not in ("agent_done", "all_done"):
-            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
         B = self.num_pairs
         seeds = list(range(B)) if env_seeds is None else [int(s) for s in env_seeds]
         if len(seeds) != B:
             raise ValueError(f"env_seeds has {len(seeds)} entries for {B} pairs")
-        spec = getattr(self.engine.model, "spec", None)
-        limit = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
-        if limit < 1:
-            raise ValueError("run_episodes needs the model's spec.max_episode_steps")
-        max_steps = limit if max_steps is None else int(max_steps)
-        if not 1 <= max_steps <= limit:
-            raise ValueError(f"max_steps must be 1 to the model's max_episode_steps ({limit}), "
-                             f"not {max_steps}")
-        if self._planned_searches is not None and self._planned_searches < max_steps:
-            raise ValueError(
-                f"run_episodes searches up to {max_steps} times per pair and a pair's arenas hold "
-                f"the whole episode: create the engine with BatchedINTMCP(..., searches={max_steps}) "
-                f"(this one was sized with searches={self._planned_searches})")
-        pop_ids = pop_probs = None
-        if other_agents is not None:
-            from posggym_baselines_amd.planning.episodes import check_population
-            other_agents = list(other_agents)
-            pop_probs = check_population(other_agents, self.engine.A)
-            pop_ids = [pol.policy_id for pol in other_agents]
+        max_steps, pop_ids, pop_probs = self._episode_guards("run_episodes", until, max_steps,
+                                                             other_agents)
         gamma = self.engine.config.discount
         pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
         start = time.time()
@@ -718,6 +769,86 @@ class BatchedINTMCP:
                 write_row(row)
             rows.append(row)
         return rows
+
+    def run_episode_queue(self, env_seeds, *, until: str = "agent_done", max_steps=None,
+                          other_agents=None, write_row=None, on_step=None):
+        """Play ``N = len(env_seeds)`` episodes (``N >= num_pairs``) on the batch's
+        ``num_pairs`` slots; returns ``N`` rows in queue order
+        (``BatchedPOMCP.run_episode_queue`` for I-NTMCP).
+
+        ``run_episodes`` parks a pair whose episode ends until the slowest one of
+        the batch is over; here the pair is reset on the device (its node blocks,
+        obs-child maps, counters and beliefs as ``reset()`` leaves them, its RNG
+        streams carried on: ``k_im_clear_pairs``) and takes the
+        next seed of a queue that lives on the device.  The assignment rule:
+        slot ``b`` starts with entry ``b`` and ``next = num_pairs``; at the end of
+        each batch step the slots whose episode finished in that step take
+        entries ``next, next + 1, ...`` in ascending slot order while entries
+        remain; a slot that finds the queue empty is retired (parked, and
+        restored when the call returns, as ``run_episodes`` restores it).
+
+        Parity: the episodes slot ``b`` plays, in order, are bit for bit the
+        episodes ``run_planning_episodes`` plays over their seeds on one
+        ``INTMCP`` keyed ``(seed, tree_key_base + b)``.  Every episode starts
+        from empty arenas, so ``searches=max_steps`` sizes the engine however
+        long the queue is.
+
+        Row keys: ``run_episodes``' plus ``slot`` and ``slot_order`` (the
+        episode's ordinal within its slot); ``num`` is the queue index.
+        ``until``, ``max_steps``, ``other_agents``, ``write_row`` and
+        ``on_step(t, self)`` are ``run_episodes``'.  For ``on_step``:
+        ``episode_queue_slots()`` is the entry each slot is playing and
+        ``episode_queue_finished()`` the final records of the episodes that ended
+        in the step just played (their slots' ``episode_states()`` are the next
+        episodes' by then).  Not offered: ``belief_acc`` / ``belief_states``.
+        """
+        from posggym_baselines_amd.planning.episodes import batch_episode_row
+        B = self.num_pairs
+        seeds = [int(s) for s in env_seeds]
+        N_ = len(seeds)
+        if N_ < B:
+            raise ValueError(f"run_episode_queue needs at least {B} env_seeds (one per pair), "
+                             f"not {N_}")
+        max_steps, pop_ids, pop_probs = self._episode_guards("run_episode_queue", until, max_steps,
+                                                             other_agents)
+        gamma = self.engine.config.discount
+        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
+        start = time.time()
+        self.engine.episodes_set_population(pop_probs)
+        self.engine.episodes_queue_begin(seeds, pow_table, max_steps, until)
+        live, t = B, 0
+        while live > 0 and t < N_ * max_steps:
+            live = self.engine.episodes_step(self.num_sims)
+            if on_step is not None:
+                on_step(t, self)
+            t += 1
+        if live > 0:
+            raise RuntimeError(f"run_episode_queue: {live} slots still playing after {t} steps")
+        res = self.engine.episodes_queue_rows()
+        self.engine.episodes_results()   # (ends the batch: the retired slots' pairs restored)
+        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
+        elapsed = time.time() - start
+        mem = psutil.Process().memory_info().rss / 1024**2
+        rows = []
+        for i in range(N_):
+            row = batch_episode_row(i, res["res"][i], elapsed, search_ms, upd_ms, steps, mem)
+            row.update(slot=int(res["slot"][i]), slot_order=int(res["slot_order"][i]))
+            if pop_ids is not None:
+                row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
+            if write_row is not None:
+                write_row(row)
+            rows.append(row)
+        return rows
+
+    def episode_queue_slots(self):
+        """The queue entry each slot of a running ``run_episode_queue`` is playing
+        (-1: retired).  ``on_step`` may read it."""
+        return self.engine.episodes_queue_slots()
+
+    def episode_queue_finished(self):
+        """The episodes that ended in the step just played: per slot the queue
+        entry (-1: none) and the episode's final ``pomcp_episode_state``."""
+        return self.engine.episodes_queue_finished()
 
     def episode_states(self):
         """Every pair's ``pomcp_episode_state`` of the running (or last) batch of

@@ -55,6 +55,16 @@ Reported per step: wall time of both routes and the device time of the update,
 the search and k_im_episode_step + the live count (intmcp_episodes_timing).
 Stored under the key ``"intmcp"``.
 
+With ``--intmcp-queue`` it times ``BatchedINTMCP.run_episode_queue`` over
+``--rounds`` x pairs seeds (a finished pair reset and refilled on the device)
+against that many successive ``run_episodes`` calls over the same seeds on one
+engine, in both ``until`` modes, each route after one untimed warm-up of its own
+on a fresh engine; the setup is ``--intmcp``'s.  Reported per mode and route as
+for ``--queue``, and for the queue the device time per step of the rank + list +
+refill kernels and of the arena clear (intmcp_episodes_queue_timing), the bytes
+the clear stored (intmcp_debug_queue_cleared_bytes) and its store bandwidth
+against ``HBM_PEAK_BYTES_PER_S``.  Stored under the key ``"intmcp_queue"``.
+
 Usage (one GPU process, under its own time limit):
 
     timeout -k 10 900 python tools/batched_episodes_timing.py \
@@ -64,6 +74,8 @@ Usage (one GPU process, under its own time limit):
     timeout -k 10 300 python tools/batched_episodes_timing.py --queue \
         --out profiles/batched_episodes_timing.json
     timeout -k 10 600 python tools/batched_episodes_timing.py --intmcp \
+        --out profiles/batched_episodes_timing.json
+    timeout -k 10 600 python tools/batched_episodes_timing.py --intmcp-queue \
         --out profiles/batched_episodes_timing.json
 """
 import argparse
@@ -329,8 +341,84 @@ def intmcp_timing(args):
     return rec, agree
 
 
+HBM_PEAK_BYTES_PER_S = 8e12   # MI355X
+
+
+def intmcp_queue_timing(args):
+    """The --intmcp-queue comparison, both until modes."""
+    import torch
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning import BatchedINTMCP, MCTSConfig
+    B = args.trees if args.trees is not None else 2048
+    S = args.sims if args.sims is not None else 64
+    model = DrivingModel()
+    max_steps = model.spec.max_episode_steps
+    seeds = list(range(args.first_seed, args.first_seed + args.rounds * B))
+    cfg = MCTSConfig(seed=0, num_sims=S, **dict(CFG, state_belief_only=False))
+    caps = {}
+
+    def route(queue, until):
+        bp = BatchedINTMCP(model, "0", cfg, B, S, searches=max_steps, device=args.device,
+                           nesting_level=1)
+        caps["bytes"] = bp.engine.capacities.bytes_per_pair(model.action_spaces["0"].n)
+        try:
+            t0 = time.perf_counter()
+            steps, upd, search, q_ms, cleared = 0, 0.0, 0.0, (0.0, 0.0), 0
+            if queue:
+                rows = bp.run_episode_queue(seeds, until=until)
+                (upd, search, _), steps = bp.engine.episodes_timing()
+                q_ms = bp.engine.episodes_queue_timing()
+                cleared = bp.engine.debug_queue_cleared_bytes()
+            else:
+                rows = []
+                for i in range(0, len(seeds), B):
+                    rows += bp.run_episodes(seeds[i:i + B], until=until)
+                    (u, s, _), n = bp.engine.episodes_timing()
+                    steps, upd, search = steps + n, upd + u, search + s
+            sec = time.perf_counter() - t0
+        finally:
+            bp.close()
+        played = int(sum(r["len"] for r in rows))
+        rec = {
+            "episodes": len(rows), "wall_s": sec, "batch_steps": steps,
+            "episode_steps_total": played, "episode_steps_per_s": played / sec,
+            "live_share_of_slot_steps": played / (B * steps),
+            "ms_per_batch_step": sec * 1e3 / steps,
+            "update_ms_per_step": upd / steps, "search_ms_per_step": search / steps,
+        }
+        if queue:
+            rec.update({
+                "rank_list_refill_ms_per_step": q_ms[0] / steps,
+                "clear_ms_per_step": q_ms[1] / steps, "clear_ms_total": q_ms[1],
+                "clear_bytes_stored": cleared,
+                "clear_bytes_per_s": cleared / (q_ms[1] * 1e-3) if q_ms[1] > 0 else 0.0,
+                "clear_share_of_hbm_peak":
+                    cleared / (q_ms[1] * 1e-3) / HBM_PEAK_BYTES_PER_S if q_ms[1] > 0 else 0.0,
+            })
+        return rec
+
+    out = {"env": "Driving-v1", "pairs": B, "sims_per_level": S, "nesting_level": 1,
+           "searches": max_steps, "rounds": args.rounds,
+           "device": torch.cuda.get_device_name(args.device)}
+    for until in ("all_done", "agent_done"):
+        route(True, until)      # untimed warm-up of both routes' kernels and shapes
+        route(False, until)
+        rec = {"run_episode_queue": route(True, until),
+               "successive_run_episodes": route(False, until)}
+        rec["queue_over_successive_steps_per_s"] = (
+            rec["run_episode_queue"]["episode_steps_per_s"] /
+            rec["successive_run_episodes"]["episode_steps_per_s"])
+        out[until] = rec
+        print(until, json.dumps(rec), flush=True)
+    out["arena_bytes_per_pair"] = caps["bytes"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--intmcp-queue", action="store_true",
+                    help="time BatchedINTMCP.run_episode_queue over --rounds x pairs seeds against "
+                         "that many successive run_episodes calls, both until modes")
     ap.add_argument("--queue", action="store_true",
                     help="time run_episode_queue over --rounds x trees seeds against that many "
                          "successive run_episodes calls")
@@ -354,6 +442,19 @@ def main():
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
 
     assert torch.cuda.is_available(), "this measurement needs the GPU"
+    if args.intmcp_queue:
+        q_rec = intmcp_queue_timing(args)
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["intmcp_queue"] = q_rec
+        print(json.dumps(q_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0
     if args.intmcp:
         im_rec, agree = intmcp_timing(args)
         rec = {}
