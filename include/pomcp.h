@@ -669,6 +669,56 @@ int pomcp_host_queue_assign(const int32_t* queue_index, const int32_t* finished,
                             int32_t num_slots, int32_t n, int32_t* next_io, int32_t* assign_out,
                             int32_t* refilled_out);
 
+/* ---- Batched episodes with root-parallel planners (additive;
+ * csrc/pomcp_episode_group.hip) -------------------------------------------
+ * group = K > 1: the num_trees trees are num_trees / K planners of K replica
+ * trees each (planner g owns trees [g*K, (g+1)*K), as pomcp_merge_roots groups
+ * them) and every PLANNER plays one episode: after the search the replicas'
+ * roots are merged on the device (pomcp_merge_roots' kernel, world = 0), the
+ * merged action steps the planner's one environment and every replica is
+ * updated with that action and the real observation.  The planner's root is
+ * absorbing only when every replica's is; a replica whose own root is
+ * absorbing does not search and merges as zeros while its siblings play on; a
+ * searched step reports K * num_sims simulations, the merged maximum depth and
+ * the merged min / max of the replicas' MinMaxStats; a step whose update made
+ * every replica absorbing reports action 0, depth 0 and no simulation.
+ *
+ * pomcp_episodes_set_group takes effect at the next pomcp_episodes_begin;
+ * group >= 1 must divide num_trees (POMCP_E_INVALID otherwise); 1 (the
+ * default) is one episode per tree.  With group > 1:
+ *   - env_seeds, pomcp_episodes_results, _states and _pop_states have
+ *     num_trees / group entries, one per planner;
+ *   - pomcp_episodes_step's num_sims is per replica, *live_out counts planners;
+ *     pomcp_episodes_timing's ms[1] includes the merge and ms[2] is
+ *     k_group_episode_step + the live count;
+ *   - a planner's error is the first non-zero error of its replicas in replica
+ *     order, the update's before the search's, and surfaces from
+ *     pomcp_episodes_step with pomcp_update's / pomcp_search's text;
+ *   - pomcp_episodes_begin returns POMCP_E_UNSUPPORTED, before any launch,
+ *     with pomcp_episodes_track_states(1) or pomcp_episodes_track_belief_acc(1,
+ *     ..) in force, and so does pomcp_episodes_queue_begin;
+ *   - the root statistics (pomcp_get_root_stats) of a finished planner's
+ *     replicas are unspecified: the searches after the park rewrite them and
+ *     the exchange records with zeros.  pomcp_episodes_merged_roots returns
+ *     the record that is kept instead: out[g] (host, [num_trees / group]) is
+ *     the pomcp_merged_root of planner g's last real step, a step at which its
+ *     root was absorbing neither before nor after the update and nothing
+ *     failed (zeros before the first one).  POMCP_E_STATE without a running
+ *     batch of groups. */
+int pomcp_episodes_set_group(pomcp_ctx* ctx, int32_t group);
+int pomcp_episodes_merged_roots(pomcp_ctx* ctx, pomcp_merged_root* out);
+
+/* Host twin of the per-group decision (csrc/episode_group.h, the code
+ * k_group_episode_step runs): flags = [group][3] {root_absorbing, update error,
+ * search error} of the replicas after this step's update and search, merged =
+ * their pomcp_merged_root, num_sims = the simulations per replica.  *in_out is
+ * the planner's part of the step for pomcp_host_episode_step; *keep_out (may
+ * be NULL) = 1 if this is a real step of a planner whose root was not
+ * absorbing before it (the merged record is the one to keep). */
+int pomcp_host_episode_group_step_in(const int32_t* flags, int32_t group, int32_t num_sims,
+                                     const pomcp_merged_root* merged,
+                                     pomcp_episode_step_in* in_out, int32_t* keep_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@
 
 #include "belief_stats.h"
 #include "driving.h"
+#include "episode_group.h"
 #include "episode_queue.h"
 #include "episode_step.h"
 #include "host_exp.h"
@@ -296,6 +297,33 @@ int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
     build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
     episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
   }
+  return POMCP_OK;
+}
+
+// The per-group decision of k_group_episode_step (pomcp_episode_group.hip) on
+// the host, through the same episode_group.h: the replicas' flags in chunks of
+// kEpGroupChunk, each chunk summarised in replica order (the kernel's ballots),
+// the chunks folded in order; then the planner's part of the episode step.
+int pomcp_host_episode_group_step_in(const int32_t* flags, int32_t group, int32_t num_sims,
+                                     const pomcp_merged_root* merged,
+                                     pomcp_episode_step_in* in_out, int32_t* keep_out) {
+  if (!flags || !merged || !in_out || group < 1 || num_sims < 0 ||
+      (int64_t)group * num_sims > INT32_MAX)
+    return POMCP_E_INVALID;
+  EpGroupFlags f = ep_group_none();
+  for (int32_t k0 = 0; k0 < group; k0 += kEpGroupChunk) {
+    EpGroupFlags c = ep_group_none();
+    for (int32_t k = k0; k < group && k < k0 + kEpGroupChunk; ++k) {
+      const int32_t* r = flags + 3 * (int64_t)k;
+      if (r[0] == 0) c.any_live = 1;
+      if (c.update_error == 0) c.update_error = r[1];
+      if (c.search_error == 0) c.search_error = r[2];
+    }
+    ep_group_fold(&f, c);
+  }
+  ep_group_step_in(f, *merged, group, num_sims, in_out);
+  // (for a planner whose root was not absorbing before the step)
+  if (keep_out) *keep_out = ep_group_real(0, *in_out) ? 1 : 0;
   return POMCP_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include "host_api.cpp"
 #include "belief_stats.hip"
 #include "pomcp_episode.hip"
+#include "pomcp_episode_group.hip"   // (after pomcp_episode.hip's EpDev)
 #include "episode_belief_acc.hip"
 #include "pomcp_episode_queue.hip"
 #include "pomcp_search.hip"
@@ -107,6 +109,13 @@ struct pomcp_ctx : HostCtx {
   double q_ms[2] = {0.0, 0.0};
   hipEvent_t q_ev[3] = {nullptr, nullptr, nullptr};
   uint64_t* drop_masks = nullptr;   // [search waves] (also pomcp_debug_log_drop's)
+  // root-parallel planners (pomcp_episodes_set_group): the group size the next
+  // begin takes, the running batch's (1: one episode per tree) and its device
+  // state; the kept merged records, [num_trees / 2] (the most groups there are)
+  int32_t ep_group_want = 1;
+  int32_t ep_group = 1;
+  EpGroupDev gr{};
+  pomcp_merged_root* ep_kept_merged = nullptr;
 };
 
 // Wave-per-tree search (k_search_lds) for batches up to this many trees: one
@@ -1046,6 +1055,16 @@ int pomcp_restore(pomcp_ctx* ctx) {
 // ------------------------------------------------------------ batched episodes
 
 static unsigned episode_blocks(int B) { return (unsigned)((B + kEpThreads - 1) / kEpThreads); }
+// (groups of root-parallel replicas: one wave per group)
+static unsigned group_blocks(int G) { return (unsigned)((G + kEpGroupWaves - 1) / kEpGroupWaves); }
+
+int pomcp_episodes_set_group(pomcp_ctx* ctx, int32_t group) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (group < 1 || ctx->dp.B % group != 0)
+    return fail(ctx, POMCP_E_INVALID, "episodes_set_group: group must divide num_trees");
+  ctx->ep_group_want = group;   // from the next pomcp_episodes_begin on
+  return POMCP_OK;
+}
 
 int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
                          int32_t max_steps, int32_t until) {
@@ -1055,17 +1074,26 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     return fail(ctx, POMCP_E_INVALID, "episodes_begin: bad arguments");
   if (ctx->dp.tm && !ctx->tm_set)
     return fail(ctx, POMCP_E_STATE, "episodes_begin: pomcp_set_type_policies first");
+  const int K = ctx->ep_group_want;
+  if (K > 1 && (ctx->ep_track || ctx->ep_acc_want))
+    return fail(ctx, POMCP_E_UNSUPPORTED,
+                "episodes_begin: groups of root-parallel replicas (pomcp_episodes_set_group) play "
+                "without pomcp_episodes_track_states and pomcp_episodes_track_belief_acc");
   PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
+  const int G = B / K;   // episodes: one per group of K replicas (K = 1: per tree)
   EpDev& ep = ctx->ep;
   const size_t nB = (size_t)B;
   int rc;
   for (hipEvent_t& e : ctx->ep_ev)
     if (!e) PB_TRY(ctx, hipEventCreate(&e));
   if (!ep.out) {   // (the last one allocated: a failed attempt is started over)
+    // (the counts: a workgroup of k_episode_step, or of k_group_episode_step for
+    // the most groups a batch can have, B / 2)
+    const unsigned nparts = std::max(episode_blocks(B), group_blocks(B / 2));
     if ((rc = ctx->alloc(ep.st, nB)) != POMCP_OK || (rc = ctx->alloc(ep.kept, nB)) != POMCP_OK ||
         (rc = ctx->alloc(ep.env_seeds, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ep.part, 2 * (size_t)episode_blocks(B))) != POMCP_OK)
+        (rc = ctx->alloc(ep.part, 2 * (size_t)nparts)) != POMCP_OK)
       return rc;
     ep.in_actions = const_cast<int32_t*>(ctx->dp.in_actions);
     ep.in_obs = const_cast<uint64_t*>(ctx->dp.in_obs);
@@ -1123,20 +1151,39 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     ep.acc_part = acc.part;
     ep.acc_nparts = nparts;
   }
+  if (K > 1 && !ctx->ep_kept_merged &&
+      (rc = ctx->alloc(ctx->ep_kept_merged, (size_t)(B / 2))) != POMCP_OK)
+    return rc;
   ctx->ep_active = false;
   if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;   // (ends queue mode too)
-  if ((rc = ctx->upload(ep.env_seeds, env_seeds, nB)) != POMCP_OK ||
+  if ((rc = ctx->upload(ep.env_seeds, env_seeds, (size_t)G)) != POMCP_OK ||
       (rc = ctx->upload(ep.pow_table, pow_table, (size_t)max_steps)) != POMCP_OK)
     return rc;
   PB_TRY(ctx, hipMemsetAsync(ep.kept, 0, sizeof(pomcp_root_stats) * nB, ctx->stream));
-  with_episode_env(ctx, [&](auto e) {
-    hipLaunchKernelGGL(k_episode_reset<decltype(e)>, dim3(episode_blocks(B)), dim3(kEpThreads), 0,
-                       ctx->stream, ctx->dp, ep);
-  });
+  if (K > 1) {
+    ctx->gr.merged = ctx->merged;
+    ctx->gr.kept = ctx->ep_kept_merged;
+    ctx->gr.K = K;
+    ctx->gr.G = G;
+    ctx->gr.num_sims = 0;
+    ctx->gr.pad = 0;
+    PB_TRY(ctx, hipMemsetAsync(ctx->ep_kept_merged, 0, sizeof(pomcp_merged_root) * (size_t)G,
+                               ctx->stream));
+    with_episode_env(ctx, [&](auto e) {
+      hipLaunchKernelGGL(k_group_episode_reset<decltype(e)>, dim3(group_blocks(G)),
+                         dim3(kEpThreads), 0, ctx->stream, ctx->dp, ep, ctx->gr);
+    });
+  } else {
+    with_episode_env(ctx, [&](auto e) {
+      hipLaunchKernelGGL(k_episode_reset<decltype(e)>, dim3(episode_blocks(B)), dim3(kEpThreads), 0,
+                         ctx->stream, ctx->dp, ep);
+    });
+  }
   PB_TRY(ctx, hipGetLastError());
   // the tables were copied from the caller's memory: finish before returning
   PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->ep_active = true;
+  ctx->ep_group = K;
   ctx->ep_steps = 0;
   ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
   ctx->ep_acc = ctx->ep_acc_want;
@@ -1148,8 +1195,12 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
   if (!ctx) return POMCP_E_INVALID;
   if (num_sims < 0 || !live_out) return fail(ctx, POMCP_E_INVALID, "episodes_step: bad arguments");
   if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_step: pomcp_episodes_begin first");
+  const int K = ctx->ep_group;   // > 1: groups of root-parallel replicas
+  if (K > 1 && (int64_t)K * num_sims > INT32_MAX)
+    return fail(ctx, POMCP_E_INVALID, "episodes_step: group * num_sims overflows the statistics");
   PB_TRY(ctx, hipSetDevice(ctx->device));
   const int B = ctx->dp.B;
+  const int G = B / K;
   const bool reroot = ctx->ep_steps > 0;   // not the batch's first step
   PB_TRY(ctx, hipEventRecord(ctx->ep_ev[0], ctx->stream));
   int rc = launch_update(ctx, reroot);
@@ -1158,12 +1209,27 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
   ctx->have_root = true;
   PB_TRY(ctx, hipEventRecord(ctx->ep_ev[1], ctx->stream));
   if ((rc = launch_search(ctx, num_sims, 1)) != POMCP_OK) return rc;
+  if (K > 1) {
+    // every group's merged decision, left on the device (pomcp_merge_roots, world = 0)
+    hipLaunchKernelGGL(k_merge_roots, dim3((unsigned)G), dim3(kWave), 0, ctx->stream,
+                       (const double*)ctx->dp.merge, (int)B, (int)ctx->dp.A, (int)ctx->dp.sel, (int)K,
+                       1, ctx->merged);
+    PB_TRY(ctx, hipGetLastError());
+  }
   PB_TRY(ctx, hipEventRecord(ctx->ep_ev[2], ctx->stream));
-  const unsigned nblk = episode_blocks(B);
-  with_episode_env(ctx, [&](auto e) {
-    hipLaunchKernelGGL(k_episode_step<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
-                       ctx->dp, ctx->ep);
-  });
+  const unsigned nblk = K > 1 ? group_blocks(G) : episode_blocks(B);
+  if (K > 1) {
+    ctx->gr.num_sims = num_sims;
+    with_episode_env(ctx, [&](auto e) {
+      hipLaunchKernelGGL(k_group_episode_step<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0,
+                         ctx->stream, ctx->dp, ctx->ep, ctx->gr);
+    });
+  } else {
+    with_episode_env(ctx, [&](auto e) {
+      hipLaunchKernelGGL(k_episode_step<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
+                         ctx->dp, ctx->ep);
+    });
+  }
   PB_TRY(ctx, hipGetLastError());
   if (ctx->ep_acc) {
     // the accuracies of the trees that played, against what k_episode_step wrote
@@ -1252,7 +1318,7 @@ int pomcp_episodes_states(pomcp_ctx* ctx, pomcp_episode_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
   if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_states: pomcp_episodes_begin first");
   PB_TRY(ctx, hipSetDevice(ctx->device));
-  return ctx->fetch(out, ctx->ep.st, (size_t)ctx->dp.B);
+  return ctx->fetch(out, ctx->ep.st, (size_t)(ctx->dp.B / ctx->ep_group));
 }
 
 int pomcp_episodes_results(pomcp_ctx* ctx, pomcp_episode_result* out) {
@@ -1260,8 +1326,17 @@ int pomcp_episodes_results(pomcp_ctx* ctx, pomcp_episode_result* out) {
   std::vector<pomcp_episode_state> st((size_t)ctx->dp.B);
   const int rc = pomcp_episodes_states(ctx, st.data());
   if (rc != POMCP_OK) return rc;
-  for (int t = 0; t < ctx->dp.B; ++t) out[t] = st[t].res;
+  for (int t = 0; t < ctx->dp.B / ctx->ep_group; ++t) out[t] = st[t].res;
   return POMCP_OK;
+}
+
+int pomcp_episodes_merged_roots(pomcp_ctx* ctx, pomcp_merged_root* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active || ctx->ep_group < 2)
+    return fail(ctx, POMCP_E_STATE, "episodes_merged_roots: pomcp_episodes_set_group(K > 1), then "
+                                    "pomcp_episodes_begin");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, ctx->ep_kept_merged, (size_t)(ctx->dp.B / ctx->ep_group));
 }
 
 int pomcp_episodes_track_states(pomcp_ctx* ctx, int32_t on) {
@@ -1310,7 +1385,7 @@ int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out) {
   if (!ctx->ep_active)
     return fail(ctx, POMCP_E_STATE, "episodes_pop_states: pomcp_episodes_begin first");
   PB_TRY(ctx, hipSetDevice(ctx->device));
-  return ctx->fetch(out, ctx->ep_ps, (size_t)ctx->dp.B);
+  return ctx->fetch(out, ctx->ep_ps, (size_t)(ctx->dp.B / ctx->ep_group));
 }
 
 int pomcp_episodes_track_belief_acc(pomcp_ctx* ctx, int32_t on, int32_t per_step) {
@@ -1364,6 +1439,9 @@ int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_
   if (!env_seeds || n < ctx->dp.B)
     return fail(ctx, POMCP_E_INVALID, "episodes_queue_begin: the queue needs at least num_trees "
                                       "environment seeds");
+  if (ctx->ep_group_want > 1)
+    return fail(ctx, POMCP_E_UNSUPPORTED, "episodes_queue_begin: no queue for groups of "
+                                          "root-parallel replicas (pomcp_episodes_set_group)");
   const bool steps_want = ctx->ep_acc_steps_want;
   ctx->ep_acc_steps_want = false;   // (no per-step table in queue mode)
   int rc = pomcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);

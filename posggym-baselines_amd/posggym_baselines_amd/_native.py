@@ -406,6 +406,10 @@ SIGNATURES = [
     ("pomcp_host_log_drop", C.c_int,
      [_PU32, _PU32, _PU32, _PU32, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
     ("pomcp_host_queue_assign", C.c_int, [_P32, _P32, C.c_int32, C.c_int32, _P32, _P32, _P32]),
+    ("pomcp_episodes_set_group", C.c_int, [_CTX, C.c_int32]),
+    ("pomcp_episodes_merged_roots", C.c_int, [_CTX, C.POINTER(PomcpMergedRoot)]),
+    ("pomcp_host_episode_group_step_in", C.c_int,
+     [_P32, C.c_int32, C.c_int32, C.POINTER(PomcpMergedRoot), C.POINTER(PomcpEpisodeStepIn), _P32]),
 ]
 DEBUG_SIGNATURES = [
     ("pomcp_debug_fp_selftest", C.c_int, [_PD, _PD, C.c_int32, _PD]),

@@ -276,10 +276,10 @@ class EngineBase:
             "synthetic_obs")
         return out
 
-    def _tree_records(self, name, dtype, ctype, *args):
-        """A structured array of ``dtype`` for every tree, filled by the C
-        function ``<ABI>_<name>(ctx, *args, out)``."""
-        out = np.zeros(self._B, dtype=dtype)
+    def _tree_records(self, name, dtype, ctype, *args, n=None):
+        """A structured array of ``dtype`` for every tree (or ``n`` records),
+        filled by the C function ``<ABI>_<name>(ctx, *args, out)``."""
+        out = np.zeros(self._B if n is None else n, dtype=dtype)
         self._check(self._fn(name)(self._ctx, *args, out.ctypes.data_as(C.POINTER(ctype))), name)
         return out
 
@@ -294,13 +294,20 @@ class EngineBase:
                     "episodes_step")
         return live.value
 
+    def _episodes(self):
+        """Episodes of the batch begun last: one per tree, or one per group of
+        root-parallel replicas (``PomcpEngine.episodes_begin(..., group=K)``)."""
+        return self._B // getattr(self, "_ep_group", 1)
+
     def episodes_results(self):
-        """Every tree's ``pomcp_episode_result`` as a structured array."""
-        return self._tree_records("episodes_results", N.EPISODE_RESULT_DTYPE, N.PomcpEpisodeResult)
+        """Every tree's (group's) ``pomcp_episode_result`` as a structured array."""
+        return self._tree_records("episodes_results", N.EPISODE_RESULT_DTYPE, N.PomcpEpisodeResult,
+                                  n=self._episodes())
 
     def episodes_states(self):
-        """Every tree's whole ``pomcp_episode_state`` (tests and diagnostics)."""
-        return self._tree_records("episodes_states", N.EPISODE_STATE_DTYPE, N.PomcpEpisodeState)
+        """Every tree's (group's) whole ``pomcp_episode_state`` (tests and diagnostics)."""
+        return self._tree_records("episodes_states", N.EPISODE_STATE_DTYPE, N.PomcpEpisodeState,
+                                  n=self._episodes())
 
     def episodes_set_population(self, probs=None, mixture_index=None):
         """The other agents' population of the batches started from now on
@@ -333,7 +340,7 @@ class EngineBase:
         """Every tree's ``pomcp_episode_pop_state``: the policy index its episode
         drew from the population (-1 without one) and that policy's mixture index."""
         return self._tree_records("episodes_pop_states", N.EPISODE_POP_STATE_DTYPE,
-                                  N.PomcpEpisodePopState)
+                                  N.PomcpEpisodePopState, n=self._episodes())
 
     def episodes_timing(self):
         """Device milliseconds since ``episodes_begin`` spent in (updates,
@@ -580,19 +587,36 @@ class PomcpEngine(EngineBase):
         return out
 
     # ------------------------------------------------- batched episodes
-    def episodes_begin(self, env_seeds, pow_table, max_steps, until, track_states=False):
+    def episodes_begin(self, env_seeds, pow_table, max_steps, until, track_states=False, group=1):
         """Reset every tree and start one episode per tree on the device
-        (``pomcp_episodes_begin``); ``until`` is "agent_done" or "all_done"."""
-        seeds = np.ascontiguousarray(np.asarray(env_seeds, dtype=np.uint64).reshape(self.num_trees))
+        (``pomcp_episodes_begin``); ``until`` is "agent_done" or "all_done".
+        ``group`` = K > 1 (``pomcp_episodes_set_group``): one episode per group of
+        K root-parallel replica trees, ``num_trees // K`` seeds."""
+        group = int(group)
+        if group < 1 or self.num_trees % group:
+            raise ValueError(f"group {group} does not divide num_trees = {self.num_trees}")
+        seeds = np.asarray(env_seeds, dtype=np.uint64).reshape(-1)
+        if len(seeds) != self.num_trees // group:
+            raise ValueError(f"{len(seeds)} env_seeds for {self.num_trees // group} episodes")
+        seeds = np.ascontiguousarray(seeds)
         pw = np.ascontiguousarray(np.asarray(pow_table, dtype=np.float64))
         if len(pw) < int(max_steps):
             raise ValueError("pow_table needs max_steps entries")
         mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
         self._check(self._lib.pomcp_episodes_track_states(self._ctx, 1 if track_states else 0),
                     "episodes_track_states")
+        self._check(self._lib.pomcp_episodes_set_group(self._ctx, group), "episodes_set_group")
         self._check(self._lib.pomcp_episodes_begin(
             self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
             pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_begin")
+        self._ep_group = group
+
+    def episodes_merged_roots(self):
+        """Every group's kept ``pomcp_merged_root`` (``pomcp_episodes_merged_roots``):
+        the merged record of its last real step, as a ``PomcpMergedRoot`` array."""
+        out = (N.PomcpMergedRoot * self._episodes())()
+        self._check(self._lib.pomcp_episodes_merged_roots(self._ctx, out), "episodes_merged_roots")
+        return out
 
     def episodes_belief_counts(self):
         """``belief_counts`` against the true states the episode kernels wrote on
@@ -641,10 +665,13 @@ class PomcpEngine(EngineBase):
         mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
         self._check(self._lib.pomcp_episodes_track_states(self._ctx, 1 if track_states else 0),
                     "episodes_track_states")
+        # (a queue's slots are single trees: no groups of root-parallel replicas)
+        self._check(self._lib.pomcp_episodes_set_group(self._ctx, 1), "episodes_set_group")
         self._check(self._lib.pomcp_episodes_queue_begin(
             self._ctx, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), len(seeds),
             pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_queue_begin")
         self._queue_len = len(seeds)
+        self._ep_group = 1
 
     def debug_wave_log(self, wave):
         """One search wave's shared particle log in record order

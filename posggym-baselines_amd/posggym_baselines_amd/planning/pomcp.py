@@ -456,7 +456,8 @@ class BatchedPOMCP:
     # ------------------------------------------------------------ episodes
     def run_episodes(self, env_seeds=None, *, until: str = "agent_done",
                      belief_states: bool = False, write_row=None, on_step=None,
-                     other_agents=None, belief_acc=False, track_per_step: bool = False):
+                     other_agents=None, belief_acc=False, track_per_step: bool = False,
+                     root_parallel: int = 1):
         """Play one episode per tree against uniform random other agents, the
         whole batch in lockstep on the device; returns one result row per tree.
 
@@ -510,14 +511,44 @@ class BatchedPOMCP:
         the tracker does; ``policy`` and ``action`` are 0.0 when the particles
         carry no policy (``state_belief_only``), and ``policy`` is 0.0 for a
         true policy the planners do not model (the uniform agent included).
+
+        ``root_parallel`` = K > 1: the batch's ``num_trees = G * K`` trees are G
+        root-parallel planners of K replica trees each and every PLANNER plays
+        one episode (``pomcp_episodes_set_group``): ``env_seeds`` has G entries
+        (default ``g``) and G rows come back, ``num`` = g.  Planner ``g`` owns
+        trees ``[gK, (g+1)K)``, replica ``k`` keyed ``(seed, tree_key_base + gK +
+        k)``, and the engine's ``num_sims`` is the count PER REPLICA: it plays, bit
+        for bit, the episode the serial harness plays with a
+        ``POMCP(root_parallel=K, num_sims=K * num_sims)`` whose replicas are keyed
+        that way.  Every replica is updated with the merged action
+        (``pomcp_merge_roots``' kernel, on the device) and the real observation;
+        the planner's root is absorbing only when every replica's is, and a
+        replica whose own root is absorbing merges as zeros while its siblings
+        play on.  The planner columns of a searched step are the merged maximum
+        ``search_depth``, ``num_sims`` = K * num_sims (0 for a step whose update
+        made every replica absorbing) and the merged ``min_value`` /
+        ``max_value``.  The population (``other_agents``) is drawn per planner,
+        ``episode_states()`` returns G records, and ``episode_merged_roots()``
+        the merged record of each planner's last real step (the per-replica
+        ``root_stats()`` of a finished planner are unspecified).  Not combined
+        with ``belief_states``, ``belief_acc`` or ``run_episode_queue``
+        (``ValueError``).
         """
         from posggym_baselines_amd.planning.episodes import batch_episode_row
         if until not in ("agent_done", "all_done"):
             raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
-        B = self.num_trees
+        K = int(root_parallel)
+        if K < 1 or self.num_trees % K:
+            raise ValueError(f"root_parallel={root_parallel} does not divide num_trees = "
+                             f"{self.num_trees}")
+        if K > 1 and (belief_states or self._belief_acc_stats(belief_acc)):
+            raise ValueError("root_parallel > 1 plays without belief_states and belief_acc (the "
+                             "replicas hold K beliefs about one true state)")
+        B = self.num_trees // K   # episodes (and rows): one per planner
         seeds = list(range(B)) if env_seeds is None else [int(s) for s in env_seeds]
         if len(seeds) != B:
-            raise ValueError(f"env_seeds has {len(seeds)} entries for {B} trees")
+            raise ValueError(f"env_seeds has {len(seeds)} entries for {B} " +
+                             ("trees" if K == 1 else f"planners of {K} replica trees"))
         spec = getattr(self.engine.model, "spec", None)
         max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
         if max_steps < 1:
@@ -545,7 +576,8 @@ class BatchedPOMCP:
         start = time.time()
         self.engine.episodes_set_population(pop_probs, mix)
         self.engine.episodes_track_belief_acc(bool(acc_stats), track_per_step)
-        self.engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states)
+        self.engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states,
+                                   group=K)
         live, t = B, 0
         while live > 0 and t < max_steps:
             live = self.engine.episodes_step(self.num_sims)
@@ -595,7 +627,7 @@ class BatchedPOMCP:
 
     def run_episode_queue(self, env_seeds, *, until: str = "agent_done", other_agents=None,
                           belief_acc=False, belief_states: bool = False, write_row=None,
-                          on_step=None):
+                          on_step=None, root_parallel: int = 1):
         """Play ``N = len(env_seeds)`` episodes (``N >= num_trees``) on the batch's
         ``num_trees`` slots; returns ``N`` rows in queue order.
 
@@ -624,10 +656,15 @@ class BatchedPOMCP:
         entry each slot is playing, and ``episode_queue_finished()`` the final
         records of the episodes that ended in the step just played (their
         slots' ``episode_states()`` are the next episodes' by then).
+        ``root_parallel``: 1; a queue's slots are single trees (``ValueError``
+        for groups of replicas, which ``run_episodes`` plays).
         """
         from posggym_baselines_amd.planning.episodes import batch_episode_row
         if until not in ("agent_done", "all_done"):
             raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        if int(root_parallel) != 1:
+            raise ValueError("run_episode_queue has no root_parallel groups: its slots are single "
+                             "trees (run_episodes(root_parallel=K) plays groups)")
         B = self.num_trees
         seeds = [int(s) for s in env_seeds]
         N = len(seeds)
@@ -734,8 +771,19 @@ class BatchedPOMCP:
     def episode_states(self):
         """Every tree's device episode record (``pomcp_episode_state``) as a
         structured array: the true state, the stream counters, the last actions,
-        the flags and the result so far.  A debug getter."""
+        the flags and the result so far.  A debug getter.  One record per
+        planner of a ``run_episodes(root_parallel=K)`` batch."""
         return self.engine.episodes_states()
+
+    def episode_merged_roots(self):
+        """Every planner's kept merged record of a ``run_episodes(root_parallel=K)``
+        batch (``pomcp_episodes_merged_roots``, a ``PomcpMergedRoot`` array): the
+        ``pomcp_merged_root`` of its last real step -- its root absorbing neither
+        before nor after the update, no error -- zeros before the first one.
+        What ``root_stats()`` is to a tree of an ungrouped batch: a finished
+        planner's replicas are parked and the later searches rewrite their own
+        statistics with zeros."""
+        return self.engine.episodes_merged_roots()
 
     def episode_belief_counts(self):
         """``belief_counts`` against the true states ``run_episodes(...,

@@ -65,6 +65,18 @@ refill kernels and of the arena clear (intmcp_episodes_queue_timing), the bytes
 the clear stored (intmcp_debug_queue_cleared_bytes) and its store bandwidth
 against ``HBM_PEAK_BYTES_PER_S``.  Stored under the key ``"intmcp_queue"``.
 
+With ``--root-parallel`` it times ``run_episodes(root_parallel=K)`` (groups of
+K replica trees, one episode per planner: the merge and k_group_episode_step on
+the device) against the route it replaces on the same engine size: per step
+``engine.update`` with per-tree inputs, ``engine.search``,
+``engine.merge_roots(K)`` fetched, and ``DrivingModel.step`` per group on the
+host.  Defaults: 64 planners x 64 replicas x 64 simulations per replica (4,096
+trees).  A fresh engine per route, one untimed warm-up; the rows (length,
+return bits) are compared on every planner.  Reported per step: wall time of
+both routes and the device time of the update, the search + merge and
+k_group_episode_step + the live count.  Stored under the key
+``"root_parallel"``.
+
 Usage (one GPU process, under its own time limit):
 
     timeout -k 10 900 python tools/batched_episodes_timing.py \
@@ -76,6 +88,8 @@ Usage (one GPU process, under its own time limit):
     timeout -k 10 600 python tools/batched_episodes_timing.py --intmcp \
         --out profiles/batched_episodes_timing.json
     timeout -k 10 600 python tools/batched_episodes_timing.py --intmcp-queue \
+        --out profiles/batched_episodes_timing.json
+    timeout -k 10 300 python tools/batched_episodes_timing.py --root-parallel \
         --out profiles/batched_episodes_timing.json
 """
 import argparse
@@ -140,6 +154,114 @@ def host_route(bp, seeds, num_sims, max_steps):
         steps += 1
     sec = time.perf_counter() - t0
     return [(int(lens[b]), float(rets[b]).hex()) for b in range(B)], steps, sec
+
+
+def group_host_route(bp, seeds, K, num_sims, max_steps):
+    """The route run_episodes(root_parallel=K) replaces, on the same engine
+    size: per step ``engine.update`` with per-tree inputs (a group's action and
+    observation repeated for its K replicas), ``engine.search``,
+    ``engine.merge_roots(K)`` fetched, and every group's environment stepped on
+    the host.  Returns (rows [(len, return)], steps run, seconds)."""
+    import numpy as np
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning.episodes import UniformRandomAgents
+    G = len(seeds)
+    eng = bp.engine
+    models, others, states = [], [], []
+    keys = np.zeros(G, dtype=np.uint64)
+    for g, s in enumerate(seeds):
+        m = DrivingModel(seed=s)
+        o = UniformRandomAgents(m, s)
+        o.reset()
+        st = m.sample_initial_state()
+        keys[g] = m.obs_key(m.sample_initial_obs(st)["0"])
+        models.append(m)
+        others.append(o)
+        states.append(st)
+    t0 = time.perf_counter()
+    eng.reset()
+    last = np.full(G, -1, dtype=np.int32)
+    was_absorbing = np.zeros(G, dtype=bool)
+    done = np.zeros(G, dtype=bool)
+    lens = np.zeros(G, dtype=np.int64)
+    rets = [0.0] * G
+    steps = 0
+    while not done.all() and steps < max_steps:
+        # the planner's root is absorbing only when every replica's is
+        absorbing = eng.update(np.repeat(last, K), np.repeat(keys, K)).reshape(G, K).all(axis=1)
+        eng.search(num_sims, fetch=False)
+        merged = eng.merge_roots(K)
+        for g in np.nonzero(~done)[0]:
+            m = models[g]
+            # POMCP.step / get_action with root_parallel = K (planning/pomcp.py)
+            a = int(last[g]) if was_absorbing[g] else 0 if absorbing[g] else int(merged[g].action)
+            ts = m.step(states[g], {"0": a, "1": others[g].act("1")})
+            states[g] = ts.state
+            keys[g] = m.obs_key(ts.observations["0"])
+            last[g] = a
+            rets[g] += ts.rewards["0"]
+            lens[g] += 1
+            done[g] = ts.all_done or lens[g] >= max_steps
+        was_absorbing = absorbing
+        steps += 1
+    sec = time.perf_counter() - t0
+    return [(int(lens[g]), float(rets[g]).hex()) for g in range(G)], steps, sec
+
+
+def root_parallel_timing(args):
+    """The --root-parallel comparison; returns (record, rows agree)."""
+    import torch
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
+    K = args.replicas
+    G = args.trees if args.trees is not None else 64
+    S = args.sims if args.sims is not None else 64
+    model = DrivingModel()
+    max_steps = model.spec.max_episode_steps
+    seeds = list(range(args.first_seed, args.first_seed + G))
+
+    def fresh():
+        return BatchedPOMCP(model, "0", MCTSConfig(seed=0, num_sims=S, **CFG), G * K, S,
+                            searches=max_steps, reroot=True, device=args.device)
+
+    bp = fresh()
+    try:    # warm-up: every kernel and shape of both routes
+        bp.run_episodes(seeds, until="all_done", root_parallel=K)
+        bp.engine.merge_roots(K)
+    finally:
+        bp.close()
+    bp = fresh()
+    try:
+        t0 = time.perf_counter()
+        rows = bp.run_episodes(seeds, until="all_done", root_parallel=K)
+        dev_sec = time.perf_counter() - t0
+        (upd_ms, search_ms, step_ms), dev_steps = bp.engine.episodes_timing()
+    finally:
+        bp.close()
+    bp = fresh()
+    try:
+        host_rows, host_steps, host_sec = group_host_route(bp, seeds, K, S, max_steps)
+    finally:
+        bp.close()
+    agree = [(r["len"], float(r["return"]).hex()) for r in rows] == host_rows
+    dev_ms = dev_sec * 1e3 / dev_steps
+    host_ms = host_sec * 1e3 / host_steps
+    rec = {
+        "env": "Driving-v1", "planners": G, "replicas": K, "trees": G * K,
+        "sims_per_replica": S, "until": "all_done",
+        "device": torch.cuda.get_device_name(args.device),
+        "episode_steps_total": int(sum(r["len"] for r in rows)),
+        "run_episodes_steps": dev_steps, "run_episodes_s": dev_sec,
+        "run_episodes_ms_per_step": dev_ms,
+        "update_ms_per_step": upd_ms / dev_steps,
+        "search_and_merge_ms_per_step": search_ms / dev_steps,
+        "k_group_episode_step_ms_per_step": step_ms / dev_steps,
+        "host_route_steps": host_steps, "host_route_s": host_sec,
+        "host_route_ms_per_step": host_ms,
+        "host_over_run_episodes": host_ms / dev_ms,
+        "rows_agree": bool(agree),
+    }
+    return rec, agree
 
 
 def belief_acc_timing(fresh, seeds, max_steps):
@@ -435,6 +557,11 @@ def main():
     ap.add_argument("--out", default="-", help="JSON record path ('-': stdout only)")
     ap.add_argument("--belief-acc", action="store_true",
                     help="time run_episodes(belief_acc=True) against the on_step route")
+    ap.add_argument("--root-parallel", action="store_true",
+                    help="time run_episodes(root_parallel=--replicas) against update + search + "
+                         "merge_roots + a host step per group (defaults: 64 planners, 64 "
+                         "simulations per replica; --trees counts planners)")
+    ap.add_argument("--replicas", type=int, default=64, help="--root-parallel: replicas per planner")
     args = ap.parse_args()
 
     import torch
@@ -442,6 +569,19 @@ def main():
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
 
     assert torch.cuda.is_available(), "this measurement needs the GPU"
+    if args.root_parallel:
+        rp_rec, agree = root_parallel_timing(args)
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["root_parallel"] = rp_rec
+        print(json.dumps(rp_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0 if agree else 1
     if args.intmcp_queue:
         q_rec = intmcp_queue_timing(args)
         rec = {}
