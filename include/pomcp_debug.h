@@ -60,6 +60,17 @@ int pomcp_debug_set_select_margin(pomcp_ctx* ctx, double rel);
 /* Only the first n (1..6) inline obs-child slots of each action node are used,
  * the overflow map holds the rest (tests of that path).  Before the first search. */
 int pomcp_debug_set_inline_slots(pomcp_ctx* ctx, int32_t n);
+/* The obs-child overflow map's generation (the 14-bit tag in bits 50..63 of a
+ * map key; it advances on every reset, restore, re-root and queue refill and
+ * the map is cleared when it wraps): tree b's becomes gen[b], [num_trees]
+ * values in 1..16383 (POMCP_E_INVALID otherwise).  Synchronises the context's
+ * stream first.  The map itself is not touched: entries already stored under
+ * gen[b] become live again, so a test chooses values no stored entry carries. */
+int pomcp_debug_set_map_generation(pomcp_ctx* ctx, const int32_t* gen);
+/* One tree's overflow map, counted over its whole capacity: out[0] = the slots
+ * whose generation is the tree's current one (live), out[1] = the slots of any
+ * other non-zero generation (stale), out[2] = the tree's current generation. */
+int pomcp_debug_map_scan(pomcp_ctx* ctx, int32_t tree, int64_t out[3]);
 /* Device time of k_belief_stats alone (pomcp_belief_stats without its copies):
  * after one untimed launch, `reps` launches between two events on the context
  * stream; *ms_per_launch = elapsed / reps.  states as pomcp_belief_stats. */

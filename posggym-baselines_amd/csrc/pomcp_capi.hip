@@ -1669,6 +1669,49 @@ int pomcp_debug_set_inline_slots(pomcp_ctx* ctx, int32_t n) {
   return POMCP_OK;
 }
 
+// Debug: every tree's overflow-map generation (TreeHdr.epoch) becomes gen[b]
+// (1..kEpochMask); the maps themselves are not touched, so entries already
+// stored under gen[b] would read as live again.  Tests of the generation wrap.
+int pomcp_debug_set_map_generation(pomcp_ctx* ctx, const int32_t* gen) {
+  if (!ctx || !gen) return POMCP_E_INVALID;
+  const int B = ctx->dp.B;
+  for (int t = 0; t < B; ++t)
+    if (gen[t] < 1 || gen[t] > (int32_t)kEpochMask)
+      return fail(ctx, POMCP_E_INVALID, "debug_set_map_generation: tree " + std::to_string(t) +
+                                            ": a generation outside 1.." + std::to_string(kEpochMask));
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<TreeHdr> h((size_t)B);
+  int rc = ctx->fetch(h.data(), ctx->dp.hdr, h.size());   // (synchronises the stream)
+  if (rc != POMCP_OK) return rc;
+  for (int t = 0; t < B; ++t) h[(size_t)t].epoch = gen[t];
+  if ((rc = ctx->upload(ctx->dp.hdr, h.data(), h.size())) != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (`h` is local memory)
+  return POMCP_OK;
+}
+
+// Debug: one tree's overflow map counted on the host: out = {slots of the
+// tree's current generation, slots of any other non-zero generation, the
+// current generation}.
+int pomcp_debug_map_scan(pomcp_ctx* ctx, int32_t tree, int64_t out[3]) {
+  if (!ctx || !out || tree < 0 || tree >= ctx->dp.B) return POMCP_E_INVALID;
+  TreeHdr h;
+  int rc = fetch_hdr(ctx, tree, &h);
+  if (rc != POMCP_OK) return rc;
+  std::vector<OvfSlot> map((size_t)ctx->dp.H);
+  if ((rc = ctx->fetch(map.data(), ctx->dp.ovf + (int64_t)tree * ctx->dp.H, map.size())) != POMCP_OK)
+    return rc;
+  int64_t live = 0, stale = 0;
+  for (const OvfSlot& s : map) {
+    const uint32_t g = (uint32_t)(s.key >> kEpochShift);
+    if (g == (uint32_t)h.epoch) ++live;
+    else if (g != 0u) ++stale;
+  }
+  out[0] = live;
+  out[1] = stale;
+  out[2] = h.epoch;
+  return POMCP_OK;
+}
+
 // Debug: k_search_lds's bound on waiting for a step-tree hand-off (polls; 0 =
 // the default), so a test can make every hand-off late.
 int pomcp_debug_set_spin_limit(pomcp_ctx* ctx, int32_t polls) {

@@ -419,6 +419,8 @@ DEBUG_SIGNATURES = [
     ("pomcp_debug_phase_timing", C.c_int,
      [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_int32)]),
     ("pomcp_debug_set_inline_slots", C.c_int, [C.c_void_p, C.c_int32]),
+    ("pomcp_debug_set_map_generation", C.c_int, [C.c_void_p, _P32]),
+    ("pomcp_debug_map_scan", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     ("pomcp_debug_set_select_margin", C.c_int, [C.c_void_p, C.c_double]),
     ("pomcp_debug_set_spin_limit", C.c_int, [C.c_void_p, C.c_int32]),
     ("pomcp_debug_belief_stats_ms", C.c_int,

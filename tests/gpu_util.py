@@ -98,7 +98,8 @@ def _arena_usage(engine):
 
 def batched_episodes(cfg_kwargs, num_sims, env_seeds, steps, capacities=None, usage=None,
                      inline_slots=None, probes=None, spin_limit=None, env="Driving-v1",
-                     select_margin=None, counters=None, ego="0"):
+                     select_margin=None, counters=None, ego="0", map_generation=None,
+                     map_scans=None):
     """Lockstep episodes of len(env_seeds) independent planners in ONE engine
     (tree b = planner b, env seed env_seeds[b]), `steps` real steps each.
     Returns per-tree record lists in the oracle format.  inline_slots: use only
@@ -108,14 +109,13 @@ def batched_episodes(cfg_kwargs, num_sims, env_seeds, steps, capacities=None, us
     select_margin: k_search's fast-selection margin (pomcp_debug_set_select_margin);
     counters: a list that receives each search's summed (n_exact_selects,
     n_deferred, n_cutoff); ego: the planning agent (the other acts uniformly
-    at random on the env's own stream, oracle/episode.py run_episode)."""
-    import numpy as np
-    from oracle.envs import make_model
-    from oracle.episode import ENV_TREE_BASE
-    from oracle.rng import S_ENV_POLICY_BASE, Streams
+    at random on the env's own stream, oracle/episode.py run_episode);
+    map_generation: the overflow map's generation (pomcp_debug_set_map_generation),
+    one int or one per tree, set once the engine is built and before the first
+    update; map_scans: a list that receives every tree's (live, stale,
+    generation) (pomcp_debug_map_scan) after every update."""
     from posggym_baselines_amd.planning import BatchedPOMCP
     model = product_model(env)
-    A = model.action_spaces[ego].n
     B = len(env_seeds)
     bp = BatchedPOMCP(model, ego, product_config(cfg_kwargs, num_sims), B, num_sims,
                       searches=steps, reroot=True, capacities=capacities)
@@ -128,13 +128,60 @@ def batched_episodes(cfg_kwargs, num_sims, env_seeds, steps, capacities=None, us
     if select_margin is not None:
         from posggym_baselines_amd import _native as N
         assert N.load().pomcp_debug_set_select_margin(bp.engine._ctx, float(select_margin)) == 0
+    records = [[] for _ in range(B)]
+    if map_generation is not None:
+        set_map_generation(bp.engine, map_generation)
+    scan = None if map_scans is None else lambda t: map_scans.append(map_scan(bp.engine))
+    for t, stats in lockstep(bp, env, ego, env_seeds, steps, records, usage=usage,
+                             after_update=scan):
+        if probes is not None:
+            probes.append(sum(int(st.n_probes) for st in stats))
+        if counters is not None:
+            counters.append((sum(int(st.n_exact_selects) for st in stats),
+                             sum(int(st.n_deferred) for st in stats),
+                             sum(int(st.n_cutoff) for st in stats)))
+    bp.close()
+    return records
+
+
+def set_map_generation(engine, gen):
+    """pomcp_debug_set_map_generation: one int for every tree, or one per tree."""
+    import ctypes as C
+    import numpy as np
+    from posggym_baselines_amd import _native as N
+    g = np.broadcast_to(np.asarray(gen, dtype=np.int32), (engine.num_trees,)).copy()
+    rc = N.load().pomcp_debug_set_map_generation(engine._ctx, g.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert rc == 0, rc
+
+
+def map_scan(engine, trees=None):
+    """pomcp_debug_map_scan of every tree (or `trees`): [(live, stale, generation)]."""
+    import ctypes as C
+    from posggym_baselines_amd import _native as N
+    lib, out, res = N.load(), (C.c_int64 * 3)(), []
+    for b in range(engine.num_trees) if trees is None else trees:
+        assert lib.pomcp_debug_map_scan(engine._ctx, int(b), out) == 0
+        res.append((int(out[0]), int(out[1]), int(out[2])))
+    return res
+
+
+def lockstep(bp, env, ego, env_seeds, steps, records, usage=None, after_update=None):
+    """One lockstep episode per tree of `bp` (batched_episodes), a generator:
+    appends every step's record to records[b] and yields (t, root statistics)
+    after each search, before the environments step; after_update(t) is called
+    between a step's update and its search."""
+    import numpy as np
+    from oracle.envs import make_model
+    from oracle.episode import ENV_TREE_BASE
+    from oracle.rng import S_ENV_POLICY_BASE, Streams
+    A = bp.engine.A
+    B = len(env_seeds)
     envs = []
     for s in env_seeds:
         es = Streams(s, ENV_TREE_BASE)
         e = make_model(env, es)
         st = e.sample_initial_state()
         envs.append([es, e, st, e.sample_initial_obs(st)])
-    records = [[] for _ in range(B)]
     last = np.full(B, -1, dtype=np.int32)
     for t in range(steps):
         keys = np.array([e[1].pack_obs(e[3][ego]) for e in envs], dtype=np.uint64)
@@ -143,16 +190,14 @@ def batched_episodes(cfg_kwargs, num_sims, env_seeds, steps, capacities=None, us
         bp.engine.update(last, keys)
         if usage is not None:
             usage.append(("after_update", _arena_usage(bp.engine)))
+        if after_update is not None:
+            after_update(t)
         actions = bp.search()
         stats = bp.engine.root_stats()
-        if probes is not None:
-            probes.append(sum(int(st.n_probes) for st in stats))
-        if counters is not None:
-            counters.append((sum(int(st.n_exact_selects) for st in stats),
-                             sum(int(st.n_deferred) for st in stats),
-                             sum(int(st.n_cutoff) for st in stats)))
         for b in range(B):
             records[b].append(stats_record(stats[b], A, True, actions[b], bp.engine.root_belief(b)))
+        yield t, stats
+        for b in range(B):
             es, e, st, obs = envs[b]
             acts = {i: int(actions[b]) if i == ego else
                     es.randint(S_ENV_POLICY_BASE + int(i), e.action_spaces[i].n)
@@ -160,8 +205,6 @@ def batched_episodes(cfg_kwargs, num_sims, env_seeds, steps, capacities=None, us
             ts = e.step(st, acts)
             envs[b][2], envs[b][3] = ts.state, ts.observations
         last = actions.astype(np.int32)
-    bp.close()
-    return records
 
 
 def intmcp_state_record(eng, pair, searched, action):

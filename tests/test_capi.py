@@ -296,3 +296,15 @@ def test_create_rejects_a_null_config():
     assert _create("pomcp", None) == (N.POMCP_E_INVALID, 0xDEAD)   # (*out is not touched)
     assert _create("intmcp", None) == (N.POMCP_E_INVALID, 0xDEAD)
     assert N.load().pomcp_last_error(None) == b"null context"
+
+
+def test_map_diagnostics_are_bound_and_refuse_a_null_context():
+    """pomcp_debug_set_map_generation / pomcp_debug_map_scan (include/pomcp_debug.h)."""
+    lib = N.load()
+    bound = {s[0] for s in N.DEBUG_SIGNATURES}
+    for name in ("pomcp_debug_set_map_generation", "pomcp_debug_map_scan"):
+        assert hasattr(lib, name) and name in bound, name
+    gen = (ctypes.c_int32 * 1)(1)
+    scan = (ctypes.c_int64 * 3)()
+    assert lib.pomcp_debug_set_map_generation(None, gen) == N.POMCP_E_INVALID
+    assert lib.pomcp_debug_map_scan(None, 0, scan) == N.POMCP_E_INVALID

@@ -57,11 +57,11 @@ class Recorder:
             self.acc.append(bp.episode_belief_acc().copy())
 
 
-def swap_engine(planner, model, cfg, num_sims, tree):
+def swap_engine(planner, model, cfg, num_sims, tree, ego=EGO):
     """Key a single planner like tree `tree` of a batch: (seed, tree)."""
     from posggym_baselines_amd.planning.engine import PomcpEngine
     planner._engine.close()
-    planner._engine = PomcpEngine(model, EGO, cfg, num_trees=1, num_sims=num_sims,
+    planner._engine = PomcpEngine(model, ego, cfg, num_trees=1, num_sims=num_sims,
                                   tree_key_base=tree, type_policies=planner.type_policies)
 
 

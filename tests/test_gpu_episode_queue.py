@@ -170,23 +170,25 @@ def restated_schedule(B, lens):
 
 
 @functools.lru_cache(maxsize=None)
-def serial_slot(env, slot, seeds, until, with_pop):
+def serial_slot(env, slot, seeds, until, with_pop, ego=EGO, num_sims=S):
     """The serial harness over one slot's seed sequence, on one planner keyed
     like the slot; computed once for all modes (the search kernels are
     bit-identical, tests/test_gpu_parity.py).  Returns (rows, per-episode steps,
     per-episode lists of the planner statistics of the steps that reached
-    PlanningStatTracker)."""
+    PlanningStatTracker).  ego / num_sims: the planning agent and its simulations
+    per search (tests/test_gpu_child_map.py plays the other agent)."""
     from posggym_baselines_amd.planning import (POMCP, BeliefStatTracker, EpisodeEnvView,
                                                 RandomSearchPolicy, run_planning_episodes)
     model = product_model(env)
-    cfg = product_config(TEST_CFG, S)
-    planner = POMCP(model, EGO, cfg, RandomSearchPolicy(model, EGO))
-    swap_engine(planner, model, cfg, S, slot)
+    other = next(i for i in model.possible_agents if i != ego)
+    cfg = product_config(TEST_CFG, num_sims)
+    planner = POMCP(model, ego, cfg, RandomSearchPolicy(model, ego))
+    swap_engine(planner, model, cfg, num_sims, slot, ego=ego)
     env_model = product_model(env)
     tracker = pop = None
     if with_pop:
         pop = pe_population(model)
-        tracker = BeliefStatTracker(planner, EpisodeEnvView(env_model, EGO), track_per_step=True,
+        tracker = BeliefStatTracker(planner, EpisodeEnvView(env_model, ego), track_per_step=True,
                                     stats_to_track=["state"])
     steps, tracked = [], []
 
@@ -194,11 +196,11 @@ def serial_slot(env, slot, seeds, until, with_pop):
         if t == 0:
             steps.append([])
             tracked.append(None)
-        steps[-1].append((a[EGO], a[OTHER], fhex(ts.rewards[EGO])))
+        steps[-1].append((a[ego], a[other], fhex(ts.rewards[ego])))
         # (the tracker's own lists so far: the last copy is the whole episode's)
         tracked[-1] = {k: list(planner.stat_tracker._current_stats[k]) for k in PLANNER_COLUMNS}
 
-    rows = run_planning_episodes(planner, env_model, len(seeds), EGO, env_seeds=list(seeds),
+    rows = run_planning_episodes(planner, env_model, len(seeds), ego, env_seeds=list(seeds),
                                  until=until, belief_tracker=tracker, other_agents=pop,
                                  on_step=on_step)
     planner._engine.close()
@@ -215,12 +217,13 @@ def sequential_mean(values):
     return total / len(vals) if vals else float("nan")
 
 
-def check_slot(rows, rec, slot, env, seeds, until, with_pop=False):
-    """Every episode of one slot against the serial harness."""
+def check_slot(rows, rec, slot, env, seeds, until, with_pop=False, **planner):
+    """Every episode of one slot against the serial harness (planner: serial_slot's
+    ego / num_sims)."""
     mine = sorted((r for r in rows if r["slot"] == slot), key=lambda r: r["slot_order"])
     assert [r["slot_order"] for r in mine] == list(range(len(mine)))
     srows, ssteps, stracked = serial_slot(env, slot, tuple(seeds[r["num"]] for r in mine), until,
-                                          with_pop)
+                                          with_pop, **planner)
     assert len(srows) == len(mine)
     for r, sr, ss, sk in zip(mine, srows, ssteps, stracked):
         where = (slot, r["slot_order"], r["num"])
