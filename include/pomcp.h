@@ -719,6 +719,52 @@ int pomcp_host_episode_group_step_in(const int32_t* flags, int32_t group, int32_
                                      const pomcp_merged_root* merged,
                                      pomcp_episode_step_in* in_out, int32_t* keep_out);
 
+/* ---- Episode queue of root-parallel planners (additive;
+ * csrc/pomcp_episode_group_queue.hip) --------------------------------------
+ * n >= num_trees / group episodes on the num_trees / group PLANNERS of a batch
+ * of groups: the queue's slots are the groups (group g = trees [g*group,
+ * (g+1)*group)), and the assignment rule is the episode queue's with "slot"
+ * meaning "group": group g starts with entry g, the groups whose episode
+ * finished in a pomcp_episodes_step take entries next, next + 1, ... in
+ * ascending group order, a group that finds the queue empty is retired.  Every
+ * one of a refilled group's trees is reset as pomcp_reset resets a tree (the RNG
+ * stream counters carry on) and its records leave its search wave's shared log;
+ * the group's kept merged record is zeroed and its one environment starts
+ * under the new seed (the population's policy drawn per group).
+ *
+ * pomcp_episodes_group_queue_begin takes the group size itself: it neither
+ * reads nor changes what pomcp_episodes_set_group stored (and
+ * pomcp_episodes_queue_begin goes on refusing a stored group > 1).
+ * POMCP_E_INVALID unless group >= 2 divides num_trees and n >= num_trees /
+ * group; POMCP_E_UNSUPPORTED with pomcp_episodes_track_states(1) or
+ * pomcp_episodes_track_belief_acc(1, ..) in force; every refusal comes before
+ * any launch.  pomcp_episodes_begin and pomcp_reset end the mode.  While it is
+ * active:
+ *   - pomcp_episodes_step is the grouped step (num_sims per replica) followed
+ *     by the queue's kernels; *live_out = unfinished + refilled groups;
+ *   - pomcp_episodes_queue_rows has n rows, row.slot = the group;
+ *     pomcp_episodes_queue_slots and _queue_finished have num_trees / group
+ *     entries; pomcp_episodes_queue_timing is the queue's;
+ *   - pomcp_episodes_results, _states, _pop_states and _merged_roots are the
+ *     running episodes', one per group;
+ *   - pomcp_episodes_queue_finished_merged: out[g] (host, [num_trees / group])
+ *     = the kept pomcp_merged_root of the episode that ended in group g in the
+ *     last pomcp_episodes_step, zeros where none ended.  POMCP_E_STATE without
+ *     a running queue of groups. */
+int pomcp_episodes_group_queue_begin(pomcp_ctx* ctx, int32_t group, const uint64_t* env_seeds,
+                                     int32_t n, const double* pow_table, int32_t max_steps,
+                                     int32_t until);
+int pomcp_episodes_queue_finished_merged(pomcp_ctx* ctx, pomcp_merged_root* out);
+
+/* Host twin of k_group_queue_trees' per-tree decision (csrc/episode_group_queue.h):
+ * assign[g] = pomcp_host_queue_assign's decision for group g of num_groups
+ * groups of `group` trees (num_groups * group = num_trees); masks_out[w] (one
+ * per search wave of 64 trees) has bit l set when tree 64 w + l belongs to a
+ * group that takes a new entry -- the mask k_log_drop gets.  Retiring (-1) and
+ * playing (-2) groups contribute no bit. */
+int pomcp_host_group_drop_masks(const int32_t* assign, int32_t num_groups, int32_t group,
+                                int32_t num_trees, uint64_t* masks_out);
+
 #ifdef __cplusplus
 }
 #endif

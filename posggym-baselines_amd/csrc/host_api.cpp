@@ -26,6 +26,7 @@
 #include "belief_stats.h"
 #include "driving.h"
 #include "episode_group.h"
+#include "episode_group_queue.h"
 #include "episode_queue.h"
 #include "episode_step.h"
 #include "host_exp.h"
@@ -431,6 +432,20 @@ int pomcp_host_queue_assign(const int32_t* queue_index, const int32_t* finished,
   const int32_t r = queue_refilled(done, next, n);
   *next_io = next + r;
   *refilled_out = r;
+  return POMCP_OK;
+}
+
+// k_group_queue_trees' drop masks (episode_group_queue.h): assign = k_queue_rank's
+// decisions for the G groups of K trees each, one mask per search wave.
+int pomcp_host_group_drop_masks(const int32_t* assign, int32_t num_groups, int32_t group,
+                                int32_t num_trees, uint64_t* masks_out) {
+  if (!assign || !masks_out || num_groups < 1 || group < 1 ||
+      (int64_t)num_groups * group != num_trees)
+    return POMCP_E_INVALID;
+  for (int32_t g = 0; g < num_groups; ++g)
+    if (assign[g] < kQueuePlaying) return POMCP_E_INVALID;
+  const int32_t waves = (num_trees + kGroupQueueWave - 1) / kGroupQueueWave;
+  for (int32_t w = 0; w < waves; ++w) masks_out[w] = group_wave_drop_mask(assign, group, num_trees, w);
   return POMCP_OK;
 }
 

@@ -25,6 +25,7 @@
 #include "pomcp_episode_group.hip"   // (after pomcp_episode.hip's EpDev)
 #include "episode_belief_acc.hip"
 #include "pomcp_episode_queue.hip"
+#include "pomcp_episode_group_queue.hip"   // (after both: EpGroupDev, EpQueueDev)
 #include "pomcp_search.hip"
 #include "pomcp_search_lds.hip"
 #include "../../include/intmcp.h"   // (INTMCP_MAX_TREES)
@@ -116,6 +117,10 @@ struct pomcp_ctx : HostCtx {
   int32_t ep_group = 1;
   EpGroupDev gr{};
   pomcp_merged_root* ep_kept_merged = nullptr;
+  // the episode queue of groups (pomcp_episodes_group_queue_begin): the running
+  // queue's slots are the batch's groups; its device state, [num_trees / 2] each
+  bool gq_active = false;
+  EpGroupQueueDev gq{};
 };
 
 // Wave-per-tree search (k_search_lds) for batches up to this many trees: one
@@ -385,6 +390,7 @@ int pomcp_reset(pomcp_ctx* ctx) {
   ctx->have_root = false;
   ctx->ep_active = false;   // a batch of episodes ends with its trees
   ctx->q_active = false;    // and its queue
+  ctx->gq_active = false;
   return POMCP_OK;
 }
 
@@ -1245,12 +1251,25 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     // (before the next update's scan and the new episodes' first appends)
     ctx->q.step = ctx->ep_steps;
     PB_TRY(ctx, hipEventRecord(ctx->q_ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_queue_rank, dim3(1), dim3(kRankThreads), 0, ctx->stream, ctx->ep, ctx->q, B);
+    // (a queue of groups: the slots are the G groups, then the groups' trees)
+    hipLaunchKernelGGL(k_queue_rank, dim3(1), dim3(kRankThreads), 0, ctx->stream, ctx->ep, ctx->q,
+                       ctx->gq_active ? G : B);
     PB_TRY(ctx, hipGetLastError());
-    with_episode_env(ctx, [&](auto e) {
-      hipLaunchKernelGGL(k_queue_refill<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
-                         ctx->dp, ctx->ep, ctx->q);
-    });
+    if (ctx->gq_active) {
+      with_episode_env(ctx, [&](auto e) {
+        hipLaunchKernelGGL(k_group_queue_refill<decltype(e)>, dim3(episode_blocks(G)),
+                           dim3(kEpThreads), 0, ctx->stream, ctx->dp, ctx->ep, ctx->gr, ctx->q,
+                           ctx->gq);
+      });
+      PB_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_group_queue_trees, dim3(episode_blocks(B)), dim3(kEpThreads), 0,
+                         ctx->stream, ctx->dp, ctx->ep, ctx->q, ctx->gq, (int)K);
+    } else {
+      with_episode_env(ctx, [&](auto e) {
+        hipLaunchKernelGGL(k_queue_refill<decltype(e)>, dim3(nblk), dim3(kEpThreads), 0, ctx->stream,
+                           ctx->dp, ctx->ep, ctx->q);
+      });
+    }
     PB_TRY(ctx, hipGetLastError());
     PB_TRY(ctx, hipEventRecord(ctx->q_ev[1], ctx->stream));
     hipLaunchKernelGGL(k_log_drop, dim3((unsigned)search_waves(B)), dim3(kDropThreads), 0, ctx->stream,
@@ -1433,23 +1452,14 @@ static int ensure_drop_masks(pomcp_ctx* ctx) {
   return ctx->alloc(ctx->drop_masks, (size_t)search_waves(ctx->dp.B));
 }
 
-int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
-                               const double* pow_table, int32_t max_steps, int32_t until) {
-  if (!ctx) return POMCP_E_INVALID;
-  if (!env_seeds || n < ctx->dp.B)
-    return fail(ctx, POMCP_E_INVALID, "episodes_queue_begin: the queue needs at least num_trees "
-                                      "environment seeds");
-  if (ctx->ep_group_want > 1)
-    return fail(ctx, POMCP_E_UNSUPPORTED, "episodes_queue_begin: no queue for groups of "
-                                          "root-parallel replicas (pomcp_episodes_set_group)");
-  const bool steps_want = ctx->ep_acc_steps_want;
-  ctx->ep_acc_steps_want = false;   // (no per-step table in queue mode)
-  int rc = pomcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);
-  ctx->ep_acc_steps_want = steps_want;
-  if (rc != POMCP_OK) return rc;
+// Queue mode for the batch pomcp_episodes_begin has just started: `slots` slots
+// (the trees, or the groups of a queue of groups) playing entries 0 .. slots - 1
+// of the n seeds.  The per-slot arrays are sized for num_trees slots.
+static int queue_arm(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n, int slots) {
   const int B = ctx->dp.B;
   const size_t nB = (size_t)B;
   EpQueueDev& q = ctx->q;
+  int rc;
   for (hipEvent_t& e : ctx->q_ev)
     if (!e) PB_TRY(ctx, hipEventCreate(&e));
   if ((rc = ensure_drop_masks(ctx)) != POMCP_OK) return rc;
@@ -1472,12 +1482,12 @@ int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_
   q.acc = ctx->ep_acc ? ctx->acc.rec : nullptr;
   q.n = n;
   q.step = 0;
-  std::vector<int32_t> iota(nB), minus(nB, -1);
-  for (int b = 0; b < B; ++b) iota[(size_t)b] = b;
-  const int32_t state[2] = {B, 0};
+  std::vector<int32_t> iota((size_t)slots), minus((size_t)slots, -1);
+  for (int b = 0; b < slots; ++b) iota[(size_t)b] = b;
+  const int32_t state[2] = {slots, 0};
   if ((rc = ctx->upload(q.seeds, env_seeds, (size_t)n)) != POMCP_OK ||
-      (rc = ctx->upload(q.slot_q, iota.data(), nB)) != POMCP_OK ||
-      (rc = ctx->upload(q.fin_q, minus.data(), nB)) != POMCP_OK ||
+      (rc = ctx->upload(q.slot_q, iota.data(), (size_t)slots)) != POMCP_OK ||
+      (rc = ctx->upload(q.fin_q, minus.data(), (size_t)slots)) != POMCP_OK ||
       (rc = ctx->upload(q.state, state, 2)) != POMCP_OK)
     return rc;
   PB_TRY(ctx, hipMemsetAsync(q.slot_ord, 0, sizeof(int32_t) * nB, ctx->stream));
@@ -1492,11 +1502,66 @@ int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_
   return POMCP_OK;
 }
 
+int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
+                               const double* pow_table, int32_t max_steps, int32_t until) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!env_seeds || n < ctx->dp.B)
+    return fail(ctx, POMCP_E_INVALID, "episodes_queue_begin: the queue needs at least num_trees "
+                                      "environment seeds");
+  if (ctx->ep_group_want > 1)
+    return fail(ctx, POMCP_E_UNSUPPORTED, "episodes_queue_begin: no queue for groups of "
+                                          "root-parallel replicas (pomcp_episodes_set_group)");
+  const bool steps_want = ctx->ep_acc_steps_want;
+  ctx->ep_acc_steps_want = false;   // (no per-step table in queue mode)
+  int rc = pomcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);
+  ctx->ep_acc_steps_want = steps_want;
+  if (rc != POMCP_OK) return rc;
+  return queue_arm(ctx, env_seeds, n, ctx->dp.B);
+}
+
+int pomcp_episodes_group_queue_begin(pomcp_ctx* ctx, int32_t group, const uint64_t* env_seeds,
+                                     int32_t n, const double* pow_table, int32_t max_steps,
+                                     int32_t until) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (group < 2 || ctx->dp.B % group != 0)
+    return fail(ctx, POMCP_E_INVALID, "episodes_group_queue_begin: group >= 2 must divide "
+                                      "num_trees");
+  const int G = ctx->dp.B / group;
+  if (!env_seeds || n < G)
+    return fail(ctx, POMCP_E_INVALID, "episodes_group_queue_begin: the queue needs at least "
+                                      "num_trees / group environment seeds");
+  if (ctx->ep_track || ctx->ep_acc_want)
+    return fail(ctx, POMCP_E_UNSUPPORTED,
+                "episodes_group_queue_begin: groups of root-parallel replicas play without "
+                "pomcp_episodes_track_states and pomcp_episodes_track_belief_acc");
+  int rc;
+  if (!ctx->gq.fin_merged &&   // (the last one allocated; the most groups there are)
+      ((rc = ctx->alloc(ctx->gq.key, (size_t)(ctx->dp.B / 2))) != POMCP_OK ||
+       (rc = ctx->alloc(ctx->gq.fin_merged, (size_t)(ctx->dp.B / 2))) != POMCP_OK))
+    return rc;
+  // the group size is this call's own: what pomcp_episodes_set_group stored stays
+  const int32_t want = ctx->ep_group_want;
+  ctx->ep_group_want = group;
+  rc = pomcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);
+  ctx->ep_group_want = want;
+  if (rc != POMCP_OK) return rc;
+  PB_TRY(ctx, hipMemsetAsync(ctx->gq.fin_merged, 0, sizeof(pomcp_merged_root) * (size_t)G,
+                             ctx->stream));
+  if ((rc = queue_arm(ctx, env_seeds, n, G)) != POMCP_OK) return rc;
+  ctx->gq_active = true;
+  return POMCP_OK;
+}
+
 static int queue_ready(pomcp_ctx* ctx, const char* what) {
   if (!ctx->ep_active || !ctx->q_active)
     return fail(ctx, POMCP_E_STATE, std::string(what) + ": pomcp_episodes_queue_begin first");
   PB_TRY(ctx, hipSetDevice(ctx->device));
   return POMCP_OK;
+}
+
+// The running queue's slots: the trees, or the groups of a queue of groups.
+static size_t queue_slots(const pomcp_ctx* ctx) {
+  return (size_t)(ctx->gq_active ? ctx->dp.B / ctx->ep_group : ctx->dp.B);
 }
 
 int pomcp_episodes_queue_rows(pomcp_ctx* ctx, pomcp_episode_queue_row* out) {
@@ -1509,7 +1574,7 @@ int pomcp_episodes_queue_rows(pomcp_ctx* ctx, pomcp_episode_queue_row* out) {
 int pomcp_episodes_queue_slots(pomcp_ctx* ctx, int32_t* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
   const int rc = queue_ready(ctx, "episodes_queue_slots");
-  return rc != POMCP_OK ? rc : ctx->fetch(out, (const int32_t*)ctx->q.slot_q, (size_t)ctx->dp.B);
+  return rc != POMCP_OK ? rc : ctx->fetch(out, (const int32_t*)ctx->q.slot_q, queue_slots(ctx));
 }
 
 int pomcp_episodes_queue_finished(pomcp_ctx* ctx, pomcp_episode_state* states_out,
@@ -1517,9 +1582,18 @@ int pomcp_episodes_queue_finished(pomcp_ctx* ctx, pomcp_episode_state* states_ou
   if (!ctx || !states_out || !queue_index_out) return POMCP_E_INVALID;
   int rc = queue_ready(ctx, "episodes_queue_finished");
   if (rc != POMCP_OK) return rc;
-  if ((rc = ctx->fetch(queue_index_out, (const int32_t*)ctx->q.fin_q, (size_t)ctx->dp.B)) != POMCP_OK)
+  if ((rc = ctx->fetch(queue_index_out, (const int32_t*)ctx->q.fin_q, queue_slots(ctx))) != POMCP_OK)
     return rc;
-  return ctx->fetch(states_out, (const pomcp_episode_state*)ctx->q.fin, (size_t)ctx->dp.B);
+  return ctx->fetch(states_out, (const pomcp_episode_state*)ctx->q.fin, queue_slots(ctx));
+}
+
+int pomcp_episodes_queue_finished_merged(pomcp_ctx* ctx, pomcp_merged_root* out) {
+  if (!ctx || !out) return POMCP_E_INVALID;
+  if (!ctx->ep_active || !ctx->gq_active)
+    return fail(ctx, POMCP_E_STATE, "episodes_queue_finished_merged: "
+                                    "pomcp_episodes_group_queue_begin first");
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  return ctx->fetch(out, (const pomcp_merged_root*)ctx->gq.fin_merged, queue_slots(ctx));
 }
 
 int pomcp_episodes_queue_timing(pomcp_ctx* ctx, double ms[2]) {

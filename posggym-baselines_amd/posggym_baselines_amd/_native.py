@@ -410,6 +410,10 @@ SIGNATURES = [
     ("pomcp_episodes_merged_roots", C.c_int, [_CTX, C.POINTER(PomcpMergedRoot)]),
     ("pomcp_host_episode_group_step_in", C.c_int,
      [_P32, C.c_int32, C.c_int32, C.POINTER(PomcpMergedRoot), C.POINTER(PomcpEpisodeStepIn), _P32]),
+    ("pomcp_episodes_group_queue_begin", C.c_int,
+     [_CTX, C.c_int32, _PU64, C.c_int32, _PD, C.c_int32, C.c_int32]),
+    ("pomcp_episodes_queue_finished_merged", C.c_int, [_CTX, C.POINTER(PomcpMergedRoot)]),
+    ("pomcp_host_group_drop_masks", C.c_int, [_P32, C.c_int32, C.c_int32, C.c_int32, _PU64]),
 ]
 DEBUG_SIGNATURES = [
     ("pomcp_debug_fp_selftest", C.c_int, [_PD, _PD, C.c_int32, _PD]),

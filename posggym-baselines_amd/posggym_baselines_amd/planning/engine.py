@@ -362,17 +362,19 @@ class EngineBase:
         return out[:n]
 
     def episodes_queue_slots(self):
-        """The queue entry each tree is playing (-1: retired)."""
-        out = np.zeros(self._B, dtype=np.int32)
+        """The queue entry each slot (tree, or group of a queue of groups) is
+        playing (-1: retired)."""
+        out = np.zeros(self._episodes(), dtype=np.int32)
         self._check(self._fn("episodes_queue_slots")(
             self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_slots")
         return out
 
     def episodes_queue_finished(self):
-        """The episodes that ended in the last step: per tree the queue entry
-        (-1: none) and its final ``pomcp_episode_state``."""
-        idx = np.zeros(self._B, dtype=np.int32)
-        st = np.zeros(self._B, dtype=N.EPISODE_STATE_DTYPE)
+        """The episodes that ended in the last step: per slot (tree, or group of
+        a queue of groups) the queue entry (-1: none) and its final
+        ``pomcp_episode_state``."""
+        idx = np.zeros(self._episodes(), dtype=np.int32)
+        st = np.zeros(self._episodes(), dtype=N.EPISODE_STATE_DTYPE)
         self._check(self._fn("episodes_queue_finished")(
             self._ctx, st.ctypes.data_as(C.POINTER(N.PomcpEpisodeState)),
             idx.ctypes.data_as(C.POINTER(C.c_int32))), "episodes_queue_finished")
@@ -672,6 +674,38 @@ class PomcpEngine(EngineBase):
             pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode), "episodes_queue_begin")
         self._queue_len = len(seeds)
         self._ep_group = 1
+
+    def episodes_group_queue_begin(self, env_seeds, pow_table, max_steps, until, group):
+        """``episodes_begin(..., group=K)`` on the first ``num_trees // K`` seeds,
+        then queue mode with the groups as slots
+        (``pomcp_episodes_group_queue_begin``): a group whose episode ends takes
+        the next of ``env_seeds`` (at least ``num_trees // K``) on the device."""
+        group = int(group)
+        if group < 2 or self.num_trees % group:
+            raise ValueError(f"group {group} is not a divisor >= 2 of num_trees = {self.num_trees}")
+        seeds = np.ascontiguousarray(np.asarray(env_seeds, dtype=np.uint64).reshape(-1))
+        if len(seeds) < self.num_trees // group:
+            raise ValueError(f"a queue of groups needs at least {self.num_trees // group} seeds")
+        pw = np.ascontiguousarray(np.asarray(pow_table, dtype=np.float64))
+        if len(pw) < int(max_steps):
+            raise ValueError("pow_table needs max_steps entries")
+        mode = {"agent_done": N.UNTIL_AGENT_DONE, "all_done": N.UNTIL_ALL_DONE}[until]
+        self._check(self._lib.pomcp_episodes_track_states(self._ctx, 0), "episodes_track_states")
+        self._check(self._lib.pomcp_episodes_group_queue_begin(
+            self._ctx, group, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), len(seeds),
+            pw.ctypes.data_as(C.POINTER(C.c_double)), int(max_steps), mode),
+            "episodes_group_queue_begin")
+        self._queue_len = len(seeds)
+        self._ep_group = group
+
+    def episodes_queue_finished_merged(self):
+        """Per group of a queue of groups, the kept ``pomcp_merged_root`` of the
+        episode that ended in the last step (zeros where none ended), as a
+        ``PomcpMergedRoot`` array (``pomcp_episodes_queue_finished_merged``)."""
+        out = (N.PomcpMergedRoot * self._episodes())()
+        self._check(self._lib.pomcp_episodes_queue_finished_merged(self._ctx, out),
+                    "episodes_queue_finished_merged")
+        return out
 
     def debug_wave_log(self, wave):
         """One search wave's shared particle log in record order

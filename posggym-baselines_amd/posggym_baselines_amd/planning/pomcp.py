@@ -531,8 +531,8 @@ class BatchedPOMCP:
         ``episode_states()`` returns G records, and ``episode_merged_roots()``
         the merged record of each planner's last real step (the per-replica
         ``root_stats()`` of a finished planner are unspecified).  Not combined
-        with ``belief_states``, ``belief_acc`` or ``run_episode_queue``
-        (``ValueError``).
+        with ``belief_states`` or ``belief_acc`` (``ValueError``);
+        ``run_planner_queue`` is the episode queue of such planners.
         """
         from posggym_baselines_amd.planning.episodes import batch_episode_row
         if until not in ("agent_done", "all_done"):
@@ -657,14 +657,14 @@ class BatchedPOMCP:
         records of the episodes that ended in the step just played (their
         slots' ``episode_states()`` are the next episodes' by then).
         ``root_parallel``: 1; a queue's slots are single trees (``ValueError``
-        for groups of replicas, which ``run_episodes`` plays).
+        for groups of replicas: ``run_planner_queue`` is their queue).
         """
         from posggym_baselines_amd.planning.episodes import batch_episode_row
         if until not in ("agent_done", "all_done"):
             raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
         if int(root_parallel) != 1:
             raise ValueError("run_episode_queue has no root_parallel groups: its slots are single "
-                             "trees (run_episodes(root_parallel=K) plays groups)")
+                             "trees (run_planner_queue(root_parallel=K) is the queue of groups)")
         B = self.num_trees
         seeds = [int(s) for s in env_seeds]
         N = len(seeds)
@@ -733,15 +733,121 @@ class BatchedPOMCP:
             rows.append(row)
         return rows
 
+    def run_planner_queue(self, env_seeds, *, root_parallel: int, until: str = "agent_done",
+                          other_agents=None, write_row=None, on_step=None):
+        """Play ``N = len(env_seeds)`` episodes on the batch's ``G = num_trees //
+        root_parallel`` root-parallel planners (``N >= G``); returns ``N`` rows in
+        queue order.
+
+        ``run_episode_queue`` for the planners of ``run_episodes(root_parallel=
+        K)``: the queue's slots are the G groups of K replica trees (group ``g``
+        owns trees ``[gK, (g+1)K)``) and the engine's ``num_sims`` is the count
+        per replica.  Group ``g`` starts with entry ``g``; at the end of each
+        batch step the groups whose episode finished in that step take entries
+        ``next, next + 1, ...`` in ascending group order while entries remain,
+        and a group that finds the queue empty is retired.  A refilled group is
+        reset on the device (``pomcp_episodes_group_queue_begin``): each of its
+        K trees as ``planner.reset()`` resets it, the RNG streams carried on,
+        its records dropped from the search waves' shared logs.
+
+        Parity: the episodes group ``g`` plays, in order, are bit for bit the
+        episodes ``run_planning_episodes`` plays over their seeds on one
+        ``POMCP(root_parallel=K, num_sims=K * num_sims)`` whose replicas are
+        keyed ``(seed, tree_key_base + gK + k)``.
+
+        Row keys: ``run_episode_queue``'s; ``slot`` is the group, ``slot_order``
+        the episode's ordinal within its group, ``num`` the queue index; the
+        planner columns are ``run_episodes(root_parallel=K)``'s.  ``until``,
+        ``other_agents`` (the policy drawn per group and entry), ``write_row`` and
+        ``on_step(t, self)`` are ``run_episode_queue``'s.  For ``on_step``:
+        ``episode_queue_slots()`` and ``episode_queue_finished()`` have G
+        entries, ``episode_states()`` and ``episode_merged_roots()`` are the
+        running episodes', and ``episode_queue_finished_merged()`` is the kept
+        merged record of the episodes that ended in the step just played.  Not
+        combined with ``belief_states`` or ``belief_acc``.
+        """
+        from posggym_baselines_amd.planning.episodes import batch_episode_row
+        if until not in ("agent_done", "all_done"):
+            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        K = int(root_parallel)
+        if K < 2:
+            raise ValueError(f"run_planner_queue needs root_parallel >= 2, not {root_parallel} "
+                             "(run_episode_queue plays single trees)")
+        if self.num_trees % K:
+            raise ValueError(f"root_parallel={root_parallel} does not divide num_trees = "
+                             f"{self.num_trees}")
+        G = self.num_trees // K
+        seeds = [int(s) for s in env_seeds]
+        N = len(seeds)
+        if N < G:
+            raise ValueError(f"run_planner_queue needs at least {G} env_seeds (one per planner of "
+                             f"{K} replica trees), not {N}")
+        spec = getattr(self.engine.model, "spec", None)
+        max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
+        if max_steps < 1:
+            raise ValueError("run_planner_queue needs the model's spec.max_episode_steps")
+        if self._planned is not None:
+            searches, reroot = self._planned
+            if not reroot or searches < max_steps:
+                raise ValueError(
+                    f"run_planner_queue re-roots up to {max_steps} times per episode: create the "
+                    f"engine with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one "
+                    f"was sized with searches={searches}, reroot={reroot})")
+        pop_ids = pop_probs = mix = None
+        if other_agents is not None:
+            from posggym_baselines_amd.planning.episodes import check_population
+            other_agents = list(other_agents)
+            pop_probs = check_population(other_agents, self.engine.A)
+            pop_ids = [pol.policy_id for pol in other_agents]
+            known = self.other_policy_ids or []
+            mix = [known.index(i) if i in known else -1 for i in pop_ids]
+        gamma = self.engine.config.discount
+        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
+        start = time.time()
+        self.engine.episodes_set_population(pop_probs, mix)
+        self.engine.episodes_track_belief_acc(False, False)
+        self.engine.episodes_group_queue_begin(seeds, pow_table, max_steps, until, K)
+        live, t = G, 0
+        while live > 0 and t < N * max_steps:
+            live = self.engine.episodes_step(self.num_sims)
+            if on_step is not None:
+                on_step(t, self)
+            t += 1
+        if live > 0:
+            raise RuntimeError(f"run_planner_queue: {live} planners still playing after {t} steps")
+        res = self.engine.episodes_queue_rows()
+        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
+        elapsed = time.time() - start
+        mem = psutil.Process().memory_info().rss / 1024**2
+        rows = []
+        for i in range(N):
+            row = batch_episode_row(i, res["res"][i], elapsed, search_ms, upd_ms, steps, mem)
+            row.update(slot=int(res["slot"][i]), slot_order=int(res["slot_order"][i]))
+            if pop_ids is not None:
+                row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
+            if write_row is not None:
+                write_row(row)
+            rows.append(row)
+        return rows
+
     def episode_queue_slots(self):
-        """The queue entry each slot of a running ``run_episode_queue`` is playing
-        (-1: retired).  ``on_step`` may read it."""
+        """The queue entry each slot of a running ``run_episode_queue`` (each
+        group of a ``run_planner_queue``) is playing (-1: retired).  ``on_step``
+        may read it."""
         return self.engine.episodes_queue_slots()
 
     def episode_queue_finished(self):
-        """The episodes that ended in the step just played: per slot the queue
-        entry (-1: none) and the episode's final ``pomcp_episode_state``."""
+        """The episodes that ended in the step just played: per slot (per group
+        of a ``run_planner_queue``) the queue entry (-1: none) and the episode's
+        final ``pomcp_episode_state``."""
         return self.engine.episodes_queue_finished()
+
+    def episode_queue_finished_merged(self):
+        """Per group of a running ``run_planner_queue``, the kept merged record
+        (``pomcp_merged_root``, a ``PomcpMergedRoot`` array) of the episode that
+        ended in the step just played; zeros for a group where none ended
+        (``episode_merged_roots()`` is the next episode's by then)."""
+        return self.engine.episodes_queue_finished_merged()
 
     def _belief_acc_stats(self, belief_acc):
         """``run_episodes``' ``belief_acc`` as the tracker's ``stats_to_track``

@@ -77,6 +77,19 @@ both routes and the device time of the update, the search + merge and
 k_group_episode_step + the live count.  Stored under the key
 ``"root_parallel"``.
 
+With ``--root-parallel-queue`` it times ``run_planner_queue`` (the episode
+queue of root-parallel planners: a finished GROUP refilled on the device) over
+``--rounds`` x planners seeds against that many successive
+``run_episodes(root_parallel=K)`` calls over the same seeds on one engine, in
+both ``until`` modes, each route after one untimed warm-up of its own on a
+fresh engine; the setup is ``--root-parallel``'s.  Reported per mode and route
+as for ``--queue``, and for the queue the device time per step of
+k_group_queue_refill + k_group_queue_trees (with k_queue_rank) and of
+k_log_drop (pomcp_episodes_queue_timing).  The routes hand the later seeds to
+different planners, so only the entries both play first in the same group are
+compared (length, return bits): exit status 1 if they differ.  Stored under the
+key ``"root_parallel_queue"``.
+
 Usage (one GPU process, under its own time limit):
 
     timeout -k 10 900 python tools/batched_episodes_timing.py \
@@ -90,6 +103,8 @@ Usage (one GPU process, under its own time limit):
     timeout -k 10 600 python tools/batched_episodes_timing.py --intmcp-queue \
         --out profiles/batched_episodes_timing.json
     timeout -k 10 300 python tools/batched_episodes_timing.py --root-parallel \
+        --out profiles/batched_episodes_timing.json
+    timeout -k 10 300 python tools/batched_episodes_timing.py --root-parallel-queue \
         --out profiles/batched_episodes_timing.json
 """
 import argparse
@@ -262,6 +277,75 @@ def root_parallel_timing(args):
         "rows_agree": bool(agree),
     }
     return rec, agree
+
+
+def root_parallel_queue_timing(args):
+    """The --root-parallel-queue comparison, both until modes; returns (record,
+    the first episodes of every group agree)."""
+    import torch
+    from posggym_baselines_amd.envs import DrivingModel
+    from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
+    K = args.replicas
+    G = args.trees if args.trees is not None else 64
+    S = args.sims if args.sims is not None else 64
+    model = DrivingModel()
+    max_steps = model.spec.max_episode_steps
+    seeds = list(range(args.first_seed, args.first_seed + args.rounds * G))
+
+    def route(queue, until):
+        bp = BatchedPOMCP(model, "0", MCTSConfig(seed=0, num_sims=S, **CFG), G * K, S,
+                          searches=max_steps, reroot=True, device=args.device)
+        try:
+            t0 = time.perf_counter()
+            steps, upd, search, q_ms = 0, 0.0, 0.0, (0.0, 0.0)
+            if queue:
+                rows = bp.run_planner_queue(seeds, root_parallel=K, until=until)
+                (upd, search, _), steps = bp.engine.episodes_timing()
+                q_ms = bp.engine.episodes_queue_timing()
+            else:
+                rows = []
+                for i in range(0, len(seeds), G):
+                    rows += bp.run_episodes(seeds[i:i + G], until=until, root_parallel=K)
+                    (u, s, _), n = bp.engine.episodes_timing()
+                    steps, upd, search = steps + n, upd + u, search + s
+            sec = time.perf_counter() - t0
+        finally:
+            bp.close()
+        played = int(sum(r["len"] for r in rows))
+        rec = {
+            "episodes": len(rows), "wall_s": sec, "batch_steps": steps,
+            "episode_steps_total": played, "episode_steps_per_s": played / sec,
+            "live_share_of_group_steps": played / (G * steps),
+            "ms_per_batch_step": sec * 1e3 / steps,
+            "update_ms_per_step": upd / steps, "search_and_merge_ms_per_step": search / steps,
+        }
+        if queue:
+            rec.update({"rank_refill_trees_ms_per_step": q_ms[0] / steps,
+                        "k_log_drop_ms_per_step": q_ms[1] / steps})
+        return rec, rows
+
+    out = {"env": "Driving-v1", "planners": G, "replicas": K, "trees": G * K,
+           "sims_per_replica": S, "rounds": args.rounds,
+           "device": torch.cuda.get_device_name(args.device)}
+    agree = True
+    for until in ("all_done", "agent_done"):
+        route(True, until)      # untimed warm-up of both routes' kernels and shapes
+        route(False, until)
+        q_rec, q_rows = route(True, until)
+        s_rec, s_rows = route(False, until)
+        # entry g < G is group g's first episode on both routes, from fresh engines
+        firsts = [i for i, r in enumerate(q_rows) if r["slot_order"] == 0 and r["slot"] == i]
+        same = len(firsts) == G and all(
+            (q_rows[i]["len"], float(q_rows[i]["return"]).hex()) ==
+            (s_rows[i]["len"], float(s_rows[i]["return"]).hex()) for i in firsts)
+        agree = agree and same
+        rec = {"run_planner_queue": q_rec, "successive_run_episodes": s_rec,
+               "queue_over_successive_steps_per_s":
+                   q_rec["episode_steps_per_s"] / s_rec["episode_steps_per_s"],
+               "first_episodes_compared": len(firsts), "first_episodes_agree": bool(same)}
+        out[until] = rec
+        print(until, json.dumps(rec), flush=True)
+    return out, agree
 
 
 def belief_acc_timing(fresh, seeds, max_steps):
@@ -561,7 +645,12 @@ def main():
                     help="time run_episodes(root_parallel=--replicas) against update + search + "
                          "merge_roots + a host step per group (defaults: 64 planners, 64 "
                          "simulations per replica; --trees counts planners)")
-    ap.add_argument("--replicas", type=int, default=64, help="--root-parallel: replicas per planner")
+    ap.add_argument("--replicas", type=int, default=64,
+                    help="--root-parallel, --root-parallel-queue: replicas per planner")
+    ap.add_argument("--root-parallel-queue", action="store_true",
+                    help="time run_planner_queue over --rounds x planners seeds against that many "
+                         "successive run_episodes(root_parallel=--replicas) calls, both until "
+                         "modes (the --root-parallel setup)")
     args = ap.parse_args()
 
     import torch
@@ -569,6 +658,19 @@ def main():
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
 
     assert torch.cuda.is_available(), "this measurement needs the GPU"
+    if args.root_parallel_queue:
+        q_rec, agree = root_parallel_queue_timing(args)
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["root_parallel_queue"] = q_rec
+        print(json.dumps(q_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0 if agree else 1
     if args.root_parallel:
         rp_rec, agree = root_parallel_timing(args)
         rec = {}
