@@ -92,6 +92,15 @@ int pomcp_debug_get_wave_log(pomcp_ctx* ctx, int32_t wave, uint32_t* ids, uint32
  * l = drop the records of tree lane l).  The trees' own log counts are not
  * touched: a test of the kernel, not a way to reset a tree. */
 int pomcp_debug_log_drop(pomcp_ctx* ctx, const uint64_t* masks);
+/* The context's environment step and observation key on the device, through
+ * the device functions the search kernels call, one case per lane: for case i,
+ * in[5i..5i+4] = {state[0], state[1], the ego's action, the other agent's
+ * action, the execution-order draw j (Driving: 0 = agent 1 moves first;
+ * PursuitEvasion: ignored)} and out[8i..8i+7] = {next[0], next[1], the ego's
+ * reward's low and high words, its done flag, its observation key's low and
+ * high words, 0}.  The ego is the context's.  States must be ones the model
+ * produces (a Driving vehicle's min-distance field at most its cell's distance). */
+int pomcp_debug_env_step(pomcp_ctx* ctx, const uint32_t* in, int32_t n, uint32_t* out);
 #ifdef __cplusplus
 }
 #endif

@@ -39,9 +39,19 @@
 using namespace pb;
 
 namespace {
+// (the tables of the calling thread's last grid are kept: a host episode loop or
+// a test steps one grid many times, and building them is most of a step's cost)
 void make_model(const pomcp_grid* g, DrvModel* m) {
-  std::memcpy(&m->g, g, sizeof(DrvGrid));
-  build_model_tables(m->g, m);
+  static_assert(sizeof(pomcp_grid) == sizeof(DrvGrid), "pomcp_grid is DrvGrid's layout");
+  thread_local DrvModel last;
+  thread_local bool have = false;
+  if (!have || std::memcmp(&last.g, g, sizeof(DrvGrid)) != 0) {
+    have = false;
+    std::memcpy(&last.g, g, sizeof(DrvGrid));
+    build_model_tables(last.g, &last);
+    have = true;
+  }
+  *m = last;
 }
 }  // namespace
 

@@ -1643,6 +1643,33 @@ int pomcp_debug_log_drop(pomcp_ctx* ctx, const uint64_t* masks) {
   return POMCP_OK;
 }
 
+// Debug: the context's Env::step and Env::obs_key on the device, one case per
+// lane (k_env_selftest): the device functions k_search steps its trees with.
+int pomcp_debug_env_step(pomcp_ctx* ctx, const uint32_t* in, int32_t n, uint32_t* out) {
+  if (!ctx || !in || !out || n <= 0) return POMCP_E_INVALID;
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  uint32_t *din = nullptr, *dout = nullptr;
+  PB_TRY(ctx, hipMalloc(&din, sizeof(uint32_t) * 5 * (size_t)n));
+  hipError_t e = hipMalloc(&dout, sizeof(uint32_t) * 8 * (size_t)n);
+  if (e == hipSuccess) e = hipMemcpyAsync(din, in, sizeof(uint32_t) * 5 * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (ctx->dp.env == POMCP_ENV_PURSUIT_EVASION)
+      hipLaunchKernelGGL(k_env_selftest<EnvPursuitEvasion>, grid, block, 0, ctx->stream, ctx->dp.model,
+                         ctx->dp.ego, (const uint32_t*)din, (int)n, dout);
+    else
+      hipLaunchKernelGGL(k_env_selftest<EnvDriving>, grid, block, 0, ctx->stream, ctx->dp.model,
+                         ctx->dp.ego, (const uint32_t*)din, (int)n, dout);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(uint32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  PB_TRY(ctx, e);
+  return POMCP_OK;
+}
+
 // Debug: FP64 sqrt / div / add-mul on the device, for bit-exactness checks
 // against the host (include/pomcp_debug.h).
 int pomcp_debug_fp_selftest(const double* a, const double* b, int32_t n, double* out) {

@@ -2123,4 +2123,31 @@ __global__ void k_fp_selftest(const double* a, const double* b, int n, double* o
   out[4 * i + 3] = (a[i] - b[i]) / (a[i] + b[i]);
 }
 
+// Env::step and Env::obs_key as k_search calls them (model staged in LDS, one
+// case per lane), for comparison with the host model: in[5i..] = {s0, s1, a_ego,
+// a_oth, j}, out[8i..] = {n0, n1, reward lo, hi, done, key lo, hi, 0}.
+template <class Env>
+__global__ __launch_bounds__(256) void k_env_selftest(const void* model, int ego, const uint32_t* in,
+                                                      int n, uint32_t* out) {
+  __shared__ typename Env::Model sm;
+  stage_model(model, sm);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t n0, n1;
+  double r;
+  int done;
+  Env::step(sm, ego, in[5 * i], in[5 * i + 1], in[5 * i + 2], in[5 * i + 3], in[5 * i + 4], &n0, &n1,
+            &r, &done);
+  const uint64_t key = Env::obs_key(sm, ego, n0, n1);
+  uint32_t* const o = out + 8 * (int64_t)i;
+  o[0] = n0;
+  o[1] = n1;
+  o[2] = (uint32_t)__double2loint(r);
+  o[3] = (uint32_t)__double2hiint(r);
+  o[4] = (uint32_t)done;
+  o[5] = (uint32_t)key;
+  o[6] = (uint32_t)(key >> 32);
+  o[7] = 0u;
+}
+
 }  // namespace pb

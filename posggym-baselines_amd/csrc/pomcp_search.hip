@@ -174,6 +174,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   uint32_t pid = 0;   // TM: the running simulation's other-agent policy (its particle's)
   int epol = 0;       // TM: the ego policy drawn for it
   const int islots = p.islots;   // kSlots (fewer: overflow-map tests)
+  const uint32_t slot_mask = (1u << islots) - 1u;   // find_slot: the slots in use
   const uint32_t wpos0 = p.wlog[wave];
   bool app = false;          // this lane has a record to append
   LogRec rec = {0u, 0u, 0u};
@@ -309,9 +310,20 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   };
   // word k of this simulation's block of stream q (0 model, 1 the other
   // agent's), else (k >= 4) a block of its own
+  // DL > 0: a simulation draws at most DL + 1 <= 4 words of either stream, one
+  // per step, so k < 4 and the arm is compiled out.  Its steps: the tree levels
+  // at depths 0 .. d - 1 (descend stops at the child of depth DL + 1, so d <=
+  // DL + 1), then, when the level at depth d - 1 expanded a leaf, the rollout
+  // steps at rdepth = d .. p.depth_limit, and p.depth_limit == DL (launch_search)
+  // -- d + (DL - d + 1) = DL + 1 in all; the step limit only ends either loop
+  // sooner.  The rollout's own action words are the EGO's stream, the other
+  // agent's is c_a[1 - ego] (p.other).
+  static_assert(kRegPath + 1 <= 4, "DL <= kRegPath: the steps of a simulation fit one Philox block");
   auto blk_word = [&](int q, uint32_t k, uint32_t sid, uint32_t j) -> uint32_t {
     uint32_t x = rw[q][k & 3u][lid];
-    if (k >= 4u) x = philox_word(seed, tkey, sid, j);
+    if constexpr (DL == 0) {
+      if (k >= 4u) x = philox_word(seed, tkey, sid, j);
+    }
     return x;
   };
   auto la_bel = [&]() {
@@ -723,18 +735,24 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 
   // ActionNode.children[obs] among the inline slots (mcts.py:356-370): filled
   // in order, so the first invalid slot is the insertion point.  -1: all taken.
+  // Straight-line: bit q of `cand` = slot q is free or holds okey, bit q of `vld`
+  // = it is valid; the lowest candidate among the first islots wins.  (Written as
+  // a scan with a condition per slot it compiled to ~22 instructions per slot,
+  // most of them scalar: DESIGN.md §4 "Issue slots".)
   auto find_slot = [&](const uint4 (&sl)[kSlots], uint64_t okey, bool* match) -> int {
-    int ks = -1;
-    *match = false;
+    static_assert(kValidBit == 1ull << 62 && kObsMask == (1ull << 50) - 1, "the key's high word");
+    const uint32_t klo = (uint32_t)okey, khi = (uint32_t)(okey >> 32);
+    uint32_t busy = 0u, vld = 0u;   // busy: valid and another key
 #pragma unroll
-    for (int q = kSlots - 1; q >= 0; --q) {
-      const uint64_t sk = (uint64_t)sl[q].x | ((uint64_t)sl[q].y << 32);
-      const bool vb = (sk & kValidBit) != 0;
-      if (q < islots && (!vb || (sk & kObsMask) == okey)) {
-        ks = q;
-        *match = vb;
-      }
+    for (int q = 0; q < kSlots; ++q) {
+      const uint32_t vm = (uint32_t)((int32_t)(sl[q].y << 1) >> 31);   // all ones: valid
+      const uint32_t ne = (sl[q].x ^ klo) | ((sl[q].y & (uint32_t)(kObsMask >> 32)) ^ khi);
+      busy |= (ne & vm) != 0u ? 1u << q : 0u;
+      vld |= vm & (1u << q);
     }
+    const uint32_t cand = ~busy & slot_mask;
+    const int ks = __ffs((int)cand) - 1;
+    *match = ((vld >> (ks & 31)) & 1u) != 0u;   // (ks = -1: bit 31, never set)
     return ks;
   };
 

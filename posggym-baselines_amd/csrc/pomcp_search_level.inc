@@ -77,7 +77,13 @@
         tree_step(a, ao, j, &n0, &n1, &r, &done, &okey, !skipc);
         bool match = false;
         int ks = 0;
-        if (!skipc) ks = find_slot(sl, okey, &match);
+        // An unrolled pass above the last one looks up whatever skipc says (a
+        // skipping lane's result is not read: sl is zero, and the skipc arm
+        // below comes first): find_slot stays straight-line, and only a lane at
+        // its step limit skips there.  At the last pass (D = DL: skipc is
+        // wave-uniform) and in the generic loop, where whole waves skip, the
+        // condition stays and the lookup is jumped over.
+        if ((D > 0 && D < DL) || !skipc) ks = find_slot(sl, okey, &match);
         PT_MARK(12);
         const uint32_t ani = (uint32_t)(blk * A + a);
         uint32_t cid = 0;

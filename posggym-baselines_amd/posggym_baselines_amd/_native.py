@@ -433,6 +433,7 @@ DEBUG_SIGNATURES = [
     ("pomcp_debug_get_wave_log", C.c_int,
      [C.c_void_p, C.c_int32, _PU32, _PU32, _PU32, _PU32, C.c_int32, _P32]),
     ("pomcp_debug_log_drop", C.c_int, [C.c_void_p, _PU64]),
+    ("pomcp_debug_env_step", C.c_int, [C.c_void_p, _PU32, C.c_int32, _PU32]),
     ("intmcp_debug_set_softmax_slack", C.c_int, [C.c_void_p, C.c_float]),
     ("intmcp_debug_exact_draws", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("intmcp_debug_arena_scan", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
