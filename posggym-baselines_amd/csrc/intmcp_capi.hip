@@ -2,40 +2,25 @@
 // single translation unit of pomcp_capi.hip.
 #include "../../include/intmcp.h"
 #include "host_ctx.h"
+#include "host_episodes.h"
 
-struct intmcp_ctx : HostCtx {
+struct intmcp_ctx : HostCtx, EpisodeHost {
   intmcp_config cfg;
   ImParams ip{};
   std::vector<int32_t> host_out;
   std::vector<IHdr> host_hdr;
   intmcp_root_stats* dev_rstats = nullptr;   // device staging of intmcp_get_root_stats
-  // batched episodes (intmcp_episodes_begin / _step): the device records (EpDev
-  // as the POMCP layer's, without root statistics, query states or belief
-  // accuracy) and the pairs' side records, whether a batch exists and whether
-  // it has ended (its parked pairs restored), its steps and the device time of
-  // its phases (events on the stream), the other agents' population
-  EpDev ep{};
+  // batched episodes (intmcp_episodes_begin / _step; EpisodeHost holds the batch
+  // -- EpDev as the POMCP layer's, without root statistics, query states or
+  // belief accuracy -- the population and the queue): the pairs' side records
+  // and whether the batch has ended (its parked pairs restored)
   intmcp_episode_kept* ep_kept = nullptr;   // [B]
-  bool ep_active = false, ep_ended = false;
-  int32_t ep_steps = 0;
-  double ep_ms[3] = {0.0, 0.0, 0.0};
-  hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ep_pop_set = false;
-  EpPopTables host_pop{};
-  EpPopTables* dev_pop = nullptr;
+  bool ep_ended = false;
   // the per-pair reset (intmcp_reset_pairs, the episode queue): the pairs to
   // reset and their count, on the device
   int32_t* rp_list = nullptr;   // [B]
   int32_t* rp_cnt = nullptr;    // [1]
-  // the episode queue (intmcp_episodes_queue_begin): whether the running batch
-  // has one, its device state and the capacity of its per-entry arrays, the
-  // device time of its kernels ({rank + list + refill, the arena clear}) and
-  // their events
-  bool q_active = false;
-  EpQueueDev q{};
-  int32_t q_cap = 0;
-  double q_ms[2] = {0.0, 0.0};
-  hipEvent_t q_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // the episode queue's (q_ms = {rank + list + refill, the arena clear}, q_ev[0 .. 3])
   int64_t* q_cleared = nullptr;   // [B] 16 B words the clear stored for each slot's refills
   unsigned long long* dbg_scan = nullptr;   // [3] intmcp_debug_arena_scan's counts
 };
@@ -136,10 +121,7 @@ const char* intmcp_last_error(const intmcp_ctx* ctx) { return ctx ? ctx->err.c_s
 void intmcp_destroy(intmcp_ctx* ctx) {
   if (!ctx) return;
   ctx->close();
-  for (hipEvent_t e : ctx->ep_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ctx->q_ev)
-    if (e) (void)hipEventDestroy(e);
+  ctx->destroy_events();
   delete ctx;
 }
 
@@ -692,17 +674,7 @@ int intmcp_synthetic_obs(intmcp_ctx* ctx, uint64_t env_seed_base, uint64_t* obs_
 
 int intmcp_episodes_set_population(intmcp_ctx* ctx, const pomcp_episode_population* pop) {
   if (!ctx) return POMCP_E_INVALID;
-  if (!pop) {
-    ctx->ep_pop_set = false;   // from the next intmcp_episodes_begin on
-    return POMCP_OK;
-  }
-  EpPopTables t;
-  if (!ep_pop_tables(*pop, ctx->ip.A, &t))
-    return fail(ctx, POMCP_E_INVALID, "episodes_set_population: 1..8 policies, probabilities >= 0 "
-                                      "with a positive sum");
-  ctx->host_pop = t;
-  ctx->ep_pop_set = true;
-  return POMCP_OK;
+  return ctx->set_population(ctx, pop, ctx->ip.A, false);   // from the next intmcp_episodes_begin on
 }
 
 int intmcp_episodes_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, const double* pow_table,
@@ -715,36 +687,12 @@ int intmcp_episodes_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, const doub
   const int B = ctx->ip.B;
   const size_t nB = (size_t)B;
   EpDev& ep = ctx->ep;
-  int rc;
-  for (hipEvent_t& e : ctx->ep_ev)
-    if (!e) PB_TRY(ctx, hipEventCreate(&e));
-  if (!ep.out) {   // (the last one allocated: a failed attempt is started over)
-    if ((rc = ctx->alloc(ep.st, nB)) != POMCP_OK || (rc = ctx->alloc(ep.ps, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ctx->ep_kept, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ep.env_seeds, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ep.part, 2 * (size_t)im_episode_blocks(B))) != POMCP_OK)
-      return rc;
-    ep.in_actions = const_cast<int32_t*>(ctx->ip.in_actions);
-    ep.in_obs = const_cast<uint64_t*>(ctx->ip.in_obs);
-    if ((rc = ctx->alloc(ep.out, 2)) != POMCP_OK) return rc;
-  }
-  // (an earlier, shorter table stays allocated until the context goes)
-  if ((ep.pow_table == nullptr || ep.max_steps != max_steps) &&
-      (rc = ctx->alloc(ep.pow_table, (size_t)max_steps)) != POMCP_OK)
-    return rc;
-  ep.max_steps = max_steps;
-  ep.until = until;
-  ep.pop = nullptr;
-  if (ctx->ep_pop_set) {
-    if ((!ctx->dev_pop && (rc = ctx->alloc(ctx->dev_pop, 1)) != POMCP_OK) ||
-        (rc = ctx->upload(ctx->dev_pop, &ctx->host_pop, 1)) != POMCP_OK)
-      return rc;
-    ep.pop = ctx->dev_pop;
-  }
+  int rc = ctx->prepare(ctx, nB, im_episode_blocks(B), ctx->ip.in_actions, ctx->ip.in_obs, max_steps,
+                        until);
+  if (rc != POMCP_OK) return rc;
+  if (!ctx->ep_kept && (rc = ctx->alloc(ctx->ep_kept, nB)) != POMCP_OK) return rc;
   if ((rc = intmcp_reset(ctx)) != POMCP_OK) return rc;   // (ends an earlier batch)
-  if ((rc = ctx->upload(ep.env_seeds, env_seeds, nB)) != POMCP_OK ||
-      (rc = ctx->upload(ep.pow_table, pow_table, (size_t)max_steps)) != POMCP_OK)
-    return rc;
+  if ((rc = ctx->upload_tables(ctx, env_seeds, nB, pow_table)) != POMCP_OK) return rc;
   im_with_episode_env(ctx, [&](auto e) {
     hipLaunchKernelGGL(k_im_episode_reset<decltype(e)>, dim3(im_episode_blocks(B)), dim3(kEpThreads),
                        0, ctx->stream, ctx->ip, ep, ctx->ep_kept);
@@ -752,10 +700,8 @@ int intmcp_episodes_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, const doub
   PB_TRY(ctx, hipGetLastError());
   // the tables were copied from the caller's memory: finish before returning
   PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->ep_active = true;
+  ctx->begun();
   ctx->ep_ended = false;
-  ctx->ep_steps = 0;
-  ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
   return POMCP_OK;
 }
 
@@ -803,32 +749,12 @@ int intmcp_episodes_step(intmcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     PB_TRY(ctx, hipGetLastError());
     PB_TRY(ctx, hipEventRecord(ctx->q_ev[3], ctx->stream));
   }
-  hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
-  PB_TRY(ctx, hipGetLastError());
-  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
   int32_t counts[2] = {0, 0};
-  PB_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
-                             ctx->stream));
-  int32_t qstate[2] = {0, 0};   // {next, slots refilled this step}
-  if (ctx->q_active)
-    PB_TRY(ctx, hipMemcpyAsync(qstate, ctx->q.state, sizeof(qstate), hipMemcpyDeviceToHost,
-                               ctx->stream));
-  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->ep_steps += 1;
-  for (int k = 0; k < 3; ++k) {
-    float ms = 0.f;
-    PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
-    ctx->ep_ms[k] += (double)ms;
-  }
-  if (ctx->q_active) {   // their own figures, not a part of slot 2
-    for (int k = 0; k < 3; ++k) {
-      float ms = 0.f;
-      PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->q_ev[k], ctx->q_ev[k + 1]));
-      ctx->q_ms[k == 1 ? 1 : 0] += (double)ms;
-      ctx->ep_ms[2] -= (double)ms;
-    }
-  }
-  *live_out = counts[0] + qstate[1];   // (a refilled slot plays on)
+  if ((rc = ctx->finish_step(ctx, nblk, live_out, counts)) != POMCP_OK) return rc;
+  for (int k = 0; ctx->q_active && k < 3; ++k)   // their own figures, not a part of slot 2
+    if ((rc = add_elapsed(ctx, ctx->q_ev[k], ctx->q_ev[k + 1], &ctx->q_ms[k == 1 ? 1 : 0],
+                          &ctx->ep_ms[2])) != POMCP_OK)
+      return rc;
   if (counts[1] != 0) {   // some pair failed: the update's error first, then the search's
     if ((rc = ctx->fetch(ctx->host_out.data(), ctx->ip.out, 2 * (size_t)B)) != POMCP_OK ||
         (rc = im_first_error(ctx, "update",
@@ -843,9 +769,7 @@ int intmcp_episodes_step(intmcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
 
 int intmcp_episodes_states(intmcp_ctx* ctx, pomcp_episode_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_states: intmcp_episodes_begin first");
-  PB_TRY(ctx, hipSetDevice(ctx->device));
-  return ctx->fetch(out, (const pomcp_episode_state*)ctx->ep.st, (size_t)ctx->ip.B);
+  return ctx->get_states(ctx, "intmcp", out, (size_t)ctx->ip.B);
 }
 
 int intmcp_episodes_results(intmcp_ctx* ctx, pomcp_episode_result* out) {
@@ -858,25 +782,17 @@ int intmcp_episodes_results(intmcp_ctx* ctx, pomcp_episode_result* out) {
                      ctx->stream, ctx->ip, ctx->ep_kept);
   PB_TRY(ctx, hipGetLastError());
   ctx->ep_ended = true;
-  std::vector<pomcp_episode_state> st((size_t)ctx->ip.B);
-  const int rc = intmcp_episodes_states(ctx, st.data());
-  if (rc != POMCP_OK) return rc;
-  for (int t = 0; t < ctx->ip.B; ++t) out[t] = st[t].res;
-  return POMCP_OK;
+  return ctx->get_results(ctx, "intmcp", out, (size_t)ctx->ip.B);
 }
 
 int intmcp_episodes_pop_states(intmcp_ctx* ctx, pomcp_episode_pop_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  if (!ctx->ep_active)
-    return fail(ctx, POMCP_E_STATE, "episodes_pop_states: intmcp_episodes_begin first");
-  PB_TRY(ctx, hipSetDevice(ctx->device));
-  return ctx->fetch(out, (const pomcp_episode_pop_state*)ctx->ep.ps, (size_t)ctx->ip.B);
+  return ctx->get_pop_states(ctx, "intmcp", out, (size_t)ctx->ip.B);
 }
 
 int intmcp_episodes_timing(intmcp_ctx* ctx, double ms[3], int32_t* steps) {
   if (!ctx || !ms || !steps) return POMCP_E_INVALID;
-  for (int k = 0; k < 3; ++k) ms[k] = ctx->ep_ms[k];
-  *steps = ctx->ep_steps;
+  ctx->get_timing(ms, steps);
   return POMCP_OK;
 }
 
@@ -929,85 +845,36 @@ int intmcp_episodes_queue_begin(intmcp_ctx* ctx, const uint64_t* env_seeds, int3
                                       "environment seeds");
   int rc = intmcp_episodes_begin(ctx, env_seeds, pow_table, max_steps, until);
   if (rc != POMCP_OK) return rc;
-  const int B = ctx->ip.B;
-  const size_t nB = (size_t)B;
-  EpQueueDev& q = ctx->q;
-  for (hipEvent_t& e : ctx->q_ev)
-    if (!e) PB_TRY(ctx, hipEventCreate(&e));
-  if ((rc = im_ensure_reset_list(ctx)) != POMCP_OK) return rc;
-  if (!q.fin_q) {   // (the last one allocated)
-    if ((rc = ctx->alloc(q.slot_q, nB)) != POMCP_OK || (rc = ctx->alloc(q.slot_ord, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(q.slot_start, nB)) != POMCP_OK || (rc = ctx->alloc(q.assign, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(q.state, 2)) != POMCP_OK || (rc = ctx->alloc(q.fin, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ctx->q_cleared, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(q.fin_q, nB)) != POMCP_OK)
-      return rc;
-  }
-  if (n > ctx->q_cap) {   // (an earlier, shorter queue stays allocated until the context goes)
-    ctx->q_cap = 0;
-    if ((rc = ctx->alloc(q.seeds, (size_t)n)) != POMCP_OK ||
-        (rc = ctx->alloc(q.rows, (size_t)n)) != POMCP_OK)
-      return rc;
-    ctx->q_cap = n;
-  }
-  q.drop = nullptr;   // (no shared logs: nothing to drop)
-  q.acc_in = nullptr;
-  q.acc = nullptr;
-  q.n = n;
-  q.step = 0;
-  std::vector<int32_t> iota(nB), minus(nB, -1);
-  for (int b = 0; b < B; ++b) iota[(size_t)b] = b;
-  const int32_t state[2] = {B, 0};
-  if ((rc = ctx->upload(q.seeds, env_seeds, (size_t)n)) != POMCP_OK ||
-      (rc = ctx->upload((const int32_t*)q.slot_q, iota.data(), nB)) != POMCP_OK ||
-      (rc = ctx->upload((const int32_t*)q.fin_q, minus.data(), nB)) != POMCP_OK ||
-      (rc = ctx->upload((const int32_t*)q.state, state, 2)) != POMCP_OK)
+  const size_t nB = (size_t)ctx->ip.B;
+  if ((rc = im_ensure_reset_list(ctx)) != POMCP_OK ||
+      (!ctx->q_cleared && (rc = ctx->alloc(ctx->q_cleared, nB)) != POMCP_OK))
     return rc;
-  PB_TRY(ctx, hipMemsetAsync(q.slot_ord, 0, sizeof(int32_t) * nB, ctx->stream));
-  PB_TRY(ctx, hipMemsetAsync(q.slot_start, 0, sizeof(int32_t) * nB, ctx->stream));
-  PB_TRY(ctx, hipMemsetAsync(q.rows, 0, sizeof(pomcp_episode_queue_row) * (size_t)n, ctx->stream));
+  ctx->q.drop = nullptr;   // (no shared logs: nothing to drop)
+  ctx->q.acc_in = nullptr;
+  ctx->q.acc = nullptr;
   PB_TRY(ctx, hipMemsetAsync(ctx->q_cleared, 0, sizeof(int64_t) * nB, ctx->stream));
-  // (copied from the caller's and local memory: finish before returning)
-  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->q_ms[0] = ctx->q_ms[1] = 0.0;
-  ctx->q_active = true;
-  return POMCP_OK;
-}
-
-static int im_queue_ready(intmcp_ctx* ctx, const char* what) {
-  if (!ctx->ep_active || !ctx->q_active)
-    return fail(ctx, POMCP_E_STATE, std::string(what) + ": intmcp_episodes_queue_begin first");
-  PB_TRY(ctx, hipSetDevice(ctx->device));
-  return POMCP_OK;
+  return ctx->arm_queue(ctx, env_seeds, n, ctx->ip.B, nB);
 }
 
 int intmcp_episodes_queue_rows(intmcp_ctx* ctx, pomcp_episode_queue_row* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  const int rc = im_queue_ready(ctx, "episodes_queue_rows");
-  return rc != POMCP_OK ? rc : ctx->fetch(out, (const pomcp_episode_queue_row*)ctx->q.rows,
-                                          (size_t)ctx->q.n);
+  return ctx->get_queue_rows(ctx, "intmcp", out);
 }
 
 int intmcp_episodes_queue_slots(intmcp_ctx* ctx, int32_t* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  const int rc = im_queue_ready(ctx, "episodes_queue_slots");
-  return rc != POMCP_OK ? rc : ctx->fetch(out, (const int32_t*)ctx->q.slot_q, (size_t)ctx->ip.B);
+  return ctx->get_queue_slots(ctx, "intmcp", out, (size_t)ctx->ip.B);
 }
 
 int intmcp_episodes_queue_finished(intmcp_ctx* ctx, pomcp_episode_state* states_out,
                                    int32_t* queue_index_out) {
   if (!ctx || !states_out || !queue_index_out) return POMCP_E_INVALID;
-  int rc = im_queue_ready(ctx, "episodes_queue_finished");
-  if (rc != POMCP_OK) return rc;
-  if ((rc = ctx->fetch(queue_index_out, (const int32_t*)ctx->q.fin_q, (size_t)ctx->ip.B)) != POMCP_OK)
-    return rc;
-  return ctx->fetch(states_out, (const pomcp_episode_state*)ctx->q.fin, (size_t)ctx->ip.B);
+  return ctx->get_queue_finished(ctx, "intmcp", states_out, queue_index_out, (size_t)ctx->ip.B);
 }
 
 int intmcp_episodes_queue_timing(intmcp_ctx* ctx, double ms[2]) {
   if (!ctx || !ms) return POMCP_E_INVALID;
-  ms[0] = ctx->q_ms[0];
-  ms[1] = ctx->q_ms[1];
+  ctx->get_queue_timing(ms);
   return POMCP_OK;
 }
 
@@ -1015,7 +882,7 @@ int intmcp_episodes_queue_timing(intmcp_ctx* ctx, double ms[2]) {
 // intmcp_episodes_queue_begin, from the per-slot sums k_im_queue_refill keeps.
 int intmcp_debug_queue_cleared_bytes(intmcp_ctx* ctx, int64_t* bytes) {
   if (!ctx || !bytes) return POMCP_E_INVALID;
-  const int rc0 = im_queue_ready(ctx, "debug_queue_cleared_bytes");
+  const int rc0 = ctx->queue_ready(ctx, "intmcp", "debug_queue_cleared_bytes");
   if (rc0 != POMCP_OK) return rc0;
   std::vector<int64_t> words((size_t)ctx->ip.B);
   const int rc = ctx->fetch(words.data(), (const int64_t*)ctx->q_cleared, words.size());

@@ -34,6 +34,7 @@
 #include "intmcp_episode_queue.hip"   // (after pomcp_episode_queue.hip's EpQueueDev)
 #include "../../include/pomcp_debug.h"
 #include "host_ctx.h"
+#include "host_episodes.h"
 
 using namespace pb;
 
@@ -46,7 +47,7 @@ static_assert(sizeof(pomcp_pe_grid) == 1344, "pe grid layout");
 static_assert(sizeof(Line) == 128, "block line layout");
 static_assert(sizeof(OvfSlot) == 32, "overflow slot layout");
 
-struct pomcp_ctx : HostCtx {
+struct pomcp_ctx : HostCtx, EpisodeHost {
   pomcp_config cfg;
   DevParams dp{};
   bool have_snapshot = false;
@@ -76,22 +77,9 @@ struct pomcp_ctx : HostCtx {
   bool have_root = false;
   pomcp_belief_counts* bel_out = nullptr;   // [B] device results of k_belief_stats
   uint2* bel_q = nullptr;                   // [B] its query states
-  // batched episodes (pomcp_episodes_begin / _step): the device records, whether
-  // a batch is running, its steps so far, whether the true states are tracked
-  // in bel_q, and the device time of its phases (events on the stream)
-  EpDev ep{};
-  bool ep_active = false;
+  // batched episodes (pomcp_episodes_begin / _step; EpisodeHost holds the batch,
+  // the population and the queue): whether the true states are tracked in bel_q
   bool ep_track = false;
-  int32_t ep_steps = 0;
-  double ep_ms[3] = {0.0, 0.0, 0.0};
-  // ([4], [5]: around k_episode_belief_acc)
-  hipEvent_t ep_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // the other agents' population (pomcp_episodes_set_population): the host's
-  // tables, their device copy, every tree's record
-  bool ep_pop_set = false;
-  EpPopTables host_pop{};
-  EpPopTables* dev_pop = nullptr;
-  pomcp_episode_pop_state* ep_ps = nullptr;   // [B]
   // belief accuracy on the device (pomcp_episodes_track_belief_acc): what the
   // next begin turns on, whether the running batch tracks, its device state
   bool ep_acc_want = false, ep_acc_steps_want = false;
@@ -100,15 +88,9 @@ struct pomcp_ctx : HostCtx {
   double* acc_steps_buf = nullptr;            // the per-step table and its capacity (doubles)
   int64_t acc_steps_cap = 0;
   double host_other_pi[kTmMax][POMCP_MAX_ACTIONS] = {};   // pomcp_type_policies.other_pi
-  double ep_acc_ms = 0.0;
-  // the episode queue (pomcp_episodes_queue_begin): whether the running batch
-  // has one, its device state and the capacity of its per-entry arrays, the
-  // device time of its kernels ({rank + refill, k_log_drop}) and their events
-  bool q_active = false;
-  EpQueueDev q{};
-  int32_t q_cap = 0;
-  double q_ms[2] = {0.0, 0.0};
-  hipEvent_t q_ev[3] = {nullptr, nullptr, nullptr};
+  double ep_acc_ms = 0.0;   // k_episode_belief_acc's device time, between its two events
+  hipEvent_t acc_ev[2] = {nullptr, nullptr};
+  // the episode queue's (q.drop; q_ms = {rank + refill, k_log_drop}, q_ev[0 .. 2])
   uint64_t* drop_masks = nullptr;   // [search waves] (also pomcp_debug_log_drop's)
   // root-parallel planners (pomcp_episodes_set_group): the group size the next
   // begin takes, the running batch's (1: one episode per tree) and its device
@@ -373,9 +355,8 @@ void pomcp_destroy(pomcp_ctx* ctx) {
   if (!ctx) return;
   ctx->close();
   if (ctx->snap_hdr) (void)hipFree(ctx->snap_hdr);
-  for (hipEvent_t e : ctx->ep_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ctx->q_ev)
+  ctx->destroy_events();
+  for (hipEvent_t e : ctx->acc_ev)
     if (e) (void)hipEventDestroy(e);
   delete ctx;
 }
@@ -1090,46 +1071,24 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
   const int G = B / K;   // episodes: one per group of K replicas (K = 1: per tree)
   EpDev& ep = ctx->ep;
   const size_t nB = (size_t)B;
-  int rc;
-  for (hipEvent_t& e : ctx->ep_ev)
-    if (!e) PB_TRY(ctx, hipEventCreate(&e));
-  if (!ep.out) {   // (the last one allocated: a failed attempt is started over)
-    // (the counts: a workgroup of k_episode_step, or of k_group_episode_step for
-    // the most groups a batch can have, B / 2)
-    const unsigned nparts = std::max(episode_blocks(B), group_blocks(B / 2));
-    if ((rc = ctx->alloc(ep.st, nB)) != POMCP_OK || (rc = ctx->alloc(ep.kept, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ep.env_seeds, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(ep.part, 2 * (size_t)nparts)) != POMCP_OK)
-      return rc;
-    ep.in_actions = const_cast<int32_t*>(ctx->dp.in_actions);
-    ep.in_obs = const_cast<uint64_t*>(ctx->dp.in_obs);
-    if ((rc = ctx->alloc(ep.out, 2)) != POMCP_OK) return rc;
-  }
-  // (an earlier, shorter table stays allocated until the context goes)
-  if ((ep.pow_table == nullptr || ep.max_steps != max_steps) &&
-      (rc = ctx->alloc(ep.pow_table, (size_t)max_steps)) != POMCP_OK)
-    return rc;
-  ep.max_steps = max_steps;
-  ep.until = until;
+  // (the counts: a workgroup of k_episode_step, or of k_group_episode_step for
+  // the most groups a batch can have, B / 2)
+  const unsigned nparts = std::max(episode_blocks(B), group_blocks(B / 2));
+  int rc = ctx->prepare(ctx, nB, nparts, ctx->dp.in_actions, ctx->dp.in_obs, max_steps, until);
+  if (rc != POMCP_OK) return rc;
+  if (!ep.kept && (rc = ctx->alloc(ep.kept, nB)) != POMCP_OK) return rc;
   ep.states = nullptr;
   if (ctx->ep_track) {
     if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
     ep.states = ctx->bel_q;
-  }
-  if (!ctx->ep_ps && (rc = ctx->alloc(ctx->ep_ps, nB)) != POMCP_OK) return rc;
-  ep.ps = ctx->ep_ps;
-  ep.pop = nullptr;
-  if (ctx->ep_pop_set) {
-    if ((!ctx->dev_pop && (rc = ctx->alloc(ctx->dev_pop, 1)) != POMCP_OK) ||
-        (rc = ctx->upload(ctx->dev_pop, &ctx->host_pop, 1)) != POMCP_OK)
-      return rc;
-    ep.pop = ctx->dev_pop;
   }
   ep.acc_part = nullptr;
   ep.acc_nparts = 0;
   ctx->ep_acc = false;
   if (ctx->ep_acc_want) {
     EpAccDev& acc = ctx->acc;
+    for (hipEvent_t& e : ctx->acc_ev)
+      if (!e) PB_TRY(ctx, hipEventCreate(&e));
     if ((rc = ensure_belief_buffers(ctx)) != POMCP_OK) return rc;
     ep.states = ctx->bel_q;
     const int nparts = B < kBelMaxGrid ? B : kBelMaxGrid;
@@ -1146,7 +1105,7 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     }
     acc.steps = ctx->ep_acc_steps_want ? ctx->acc_steps_buf : nullptr;
     acc.st = ep.st;
-    acc.ps = ctx->ep_ps;
+    acc.ps = ep.ps;
     acc.states = ctx->bel_q;
     // particles carry a policy on a type-based context that draws one per particle
     acc.num_other = ctx->dp.tm && !ctx->host_tm.no_mixture_draw ? ctx->host_tm.n_other : 0;
@@ -1162,9 +1121,7 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
     return rc;
   ctx->ep_active = false;
   if ((rc = pomcp_reset(ctx)) != POMCP_OK) return rc;   // (ends queue mode too)
-  if ((rc = ctx->upload(ep.env_seeds, env_seeds, (size_t)G)) != POMCP_OK ||
-      (rc = ctx->upload(ep.pow_table, pow_table, (size_t)max_steps)) != POMCP_OK)
-    return rc;
+  if ((rc = ctx->upload_tables(ctx, env_seeds, (size_t)G, pow_table)) != POMCP_OK) return rc;
   PB_TRY(ctx, hipMemsetAsync(ep.kept, 0, sizeof(pomcp_root_stats) * nB, ctx->stream));
   if (K > 1) {
     ctx->gr.merged = ctx->merged;
@@ -1188,10 +1145,8 @@ int pomcp_episodes_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, const double
   PB_TRY(ctx, hipGetLastError());
   // the tables were copied from the caller's memory: finish before returning
   PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->ep_active = true;
+  ctx->begun();
   ctx->ep_group = K;
-  ctx->ep_steps = 0;
-  ctx->ep_ms[0] = ctx->ep_ms[1] = ctx->ep_ms[2] = 0.0;
   ctx->ep_acc = ctx->ep_acc_want;
   ctx->ep_acc_ms = 0.0;
   return POMCP_OK;
@@ -1239,11 +1194,11 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
   PB_TRY(ctx, hipGetLastError());
   if (ctx->ep_acc) {
     // the accuracies of the trees that played, against what k_episode_step wrote
-    PB_TRY(ctx, hipEventRecord(ctx->ep_ev[4], ctx->stream));
+    PB_TRY(ctx, hipEventRecord(ctx->acc_ev[0], ctx->stream));
     hipLaunchKernelGGL(k_episode_belief_acc, dim3((unsigned)ctx->ep.acc_nparts), dim3(kBelThreads),
                        0, ctx->stream, ctx->dp, ctx->acc);
     PB_TRY(ctx, hipGetLastError());
-    PB_TRY(ctx, hipEventRecord(ctx->ep_ev[5], ctx->stream));
+    PB_TRY(ctx, hipEventRecord(ctx->acc_ev[1], ctx->stream));
   }
   if (ctx->q_active) {
     // the queue: the finished slots ranked, their rows written, the slots
@@ -1277,43 +1232,20 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
     PB_TRY(ctx, hipGetLastError());
     PB_TRY(ctx, hipEventRecord(ctx->q_ev[2], ctx->stream));
   }
-  hipLaunchKernelGGL(k_episode_live, dim3(1), dim3(kEpThreads), 0, ctx->stream, ctx->ep, (int)nblk);
-  PB_TRY(ctx, hipGetLastError());
-  PB_TRY(ctx, hipEventRecord(ctx->ep_ev[3], ctx->stream));
-  int32_t counts[2] = {0, 0};
-  PB_TRY(ctx, hipMemcpyAsync(counts, ctx->ep.out, sizeof(counts), hipMemcpyDeviceToHost,
-                             ctx->stream));
-  int32_t qstate[2] = {0, 0};   // {next, slots refilled this step}
-  if (ctx->q_active)
-    PB_TRY(ctx, hipMemcpyAsync(qstate, ctx->q.state, sizeof(qstate), hipMemcpyDeviceToHost,
-                               ctx->stream));
+  // (the log scan's flag comes back under the step's one synchronise)
   uint32_t lf_fail = 0u;
   if (reroot && !ctx->log_scan_legacy)
     PB_TRY(ctx, hipMemcpyAsync(&lf_fail, ctx->dp.lf_fail, sizeof(uint32_t), hipMemcpyDeviceToHost,
                                ctx->stream));
-  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->ep_steps += 1;
-  for (int k = 0; k < 3; ++k) {
-    float ms = 0.f;
-    PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[k], ctx->ep_ev[k + 1]));
-    ctx->ep_ms[k] += (double)ms;
-  }
-  if (ctx->ep_acc) {   // its own figure, not a part of slot 2
-    float ms = 0.f;
-    PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->ep_ev[4], ctx->ep_ev[5]));
-    ctx->ep_acc_ms += (double)ms;
-    ctx->ep_ms[2] -= (double)ms;
-  }
-  if (ctx->q_active) {   // their own figures, not a part of slot 2
-    for (int k = 0; k < 2; ++k) {
-      float ms = 0.f;
-      PB_TRY(ctx, hipEventElapsedTime(&ms, ctx->q_ev[k], ctx->q_ev[k + 1]));
-      ctx->q_ms[k] += (double)ms;
-      ctx->ep_ms[2] -= (double)ms;
-    }
-  }
+  int32_t counts[2] = {0, 0};
+  if ((rc = ctx->finish_step(ctx, nblk, live_out, counts)) != POMCP_OK) return rc;
+  if (ctx->ep_acc &&   // its own figure, not a part of slot 2
+      (rc = add_elapsed(ctx, ctx->acc_ev[0], ctx->acc_ev[1], &ctx->ep_acc_ms, &ctx->ep_ms[2])) != POMCP_OK)
+    return rc;
+  for (int k = 0; ctx->q_active && k < 2; ++k)   // their own figures, not a part of slot 2
+    if ((rc = add_elapsed(ctx, ctx->q_ev[k], ctx->q_ev[k + 1], &ctx->q_ms[k], &ctx->ep_ms[2])) != POMCP_OK)
+      return rc;
   if (lf_fail != 0u) return fail(ctx, POMCP_E_HIP, "update: the log scan's look-back gave up");
-  *live_out = counts[0] + qstate[1];   // (a refilled slot plays on)
   if (counts[1] != 0) {   // some tree failed: the update's error first, then the search's
     if ((rc = ctx->fetch(ctx->host_upd.data(), ctx->dp.upd_out, 2 * (size_t)B)) != POMCP_OK ||
         (rc = first_update_error(ctx)) != POMCP_OK ||
@@ -1335,18 +1267,12 @@ int pomcp_episodes_step(pomcp_ctx* ctx, int32_t num_sims, int32_t* live_out) {
 
 int pomcp_episodes_states(pomcp_ctx* ctx, pomcp_episode_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  if (!ctx->ep_active) return fail(ctx, POMCP_E_STATE, "episodes_states: pomcp_episodes_begin first");
-  PB_TRY(ctx, hipSetDevice(ctx->device));
-  return ctx->fetch(out, ctx->ep.st, (size_t)(ctx->dp.B / ctx->ep_group));
+  return ctx->get_states(ctx, "pomcp", out, (size_t)(ctx->dp.B / ctx->ep_group));
 }
 
 int pomcp_episodes_results(pomcp_ctx* ctx, pomcp_episode_result* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  std::vector<pomcp_episode_state> st((size_t)ctx->dp.B);
-  const int rc = pomcp_episodes_states(ctx, st.data());
-  if (rc != POMCP_OK) return rc;
-  for (int t = 0; t < ctx->dp.B / ctx->ep_group; ++t) out[t] = st[t].res;
-  return POMCP_OK;
+  return ctx->get_results(ctx, "pomcp", out, (size_t)(ctx->dp.B / ctx->ep_group));
 }
 
 int pomcp_episodes_merged_roots(pomcp_ctx* ctx, pomcp_merged_root* out) {
@@ -1383,28 +1309,12 @@ int pomcp_episodes_belief_stats(pomcp_ctx* ctx, pomcp_belief_counts* out) {
 
 int pomcp_episodes_set_population(pomcp_ctx* ctx, const pomcp_episode_population* pop) {
   if (!ctx) return POMCP_E_INVALID;
-  if (!pop) {
-    ctx->ep_pop_set = false;   // from the next pomcp_episodes_begin on
-    return POMCP_OK;
-  }
-  EpPopTables t;
-  if (!ep_pop_tables(*pop, ctx->dp.A, &t))
-    return fail(ctx, POMCP_E_INVALID, "episodes_set_population: 1..8 policies, probabilities >= 0 "
-                                      "with a positive sum");
-  for (int k = 0; k < t.n; ++k)
-    if (t.mix[k] < -1 || t.mix[k] >= kTmMax)
-      return fail(ctx, POMCP_E_INVALID, "episodes_set_population: mixture_index -1..7");
-  ctx->host_pop = t;
-  ctx->ep_pop_set = true;
-  return POMCP_OK;
+  return ctx->set_population(ctx, pop, ctx->dp.A, true);   // from the next pomcp_episodes_begin on
 }
 
 int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  if (!ctx->ep_active)
-    return fail(ctx, POMCP_E_STATE, "episodes_pop_states: pomcp_episodes_begin first");
-  PB_TRY(ctx, hipSetDevice(ctx->device));
-  return ctx->fetch(out, ctx->ep_ps, (size_t)(ctx->dp.B / ctx->ep_group));
+  return ctx->get_pop_states(ctx, "pomcp", out, (size_t)(ctx->dp.B / ctx->ep_group));
 }
 
 int pomcp_episodes_track_belief_acc(pomcp_ctx* ctx, int32_t on, int32_t per_step) {
@@ -1440,8 +1350,7 @@ int pomcp_episodes_belief_acc_ms(pomcp_ctx* ctx, double* ms) {
 
 int pomcp_episodes_timing(pomcp_ctx* ctx, double ms[3], int32_t* steps) {
   if (!ctx || !ms || !steps) return POMCP_E_INVALID;
-  for (int k = 0; k < 3; ++k) ms[k] = ctx->ep_ms[k];
-  *steps = ctx->ep_steps;
+  ctx->get_timing(ms, steps);
   return POMCP_OK;
 }
 
@@ -1456,50 +1365,14 @@ static int ensure_drop_masks(pomcp_ctx* ctx) {
 // (the trees, or the groups of a queue of groups) playing entries 0 .. slots - 1
 // of the n seeds.  The per-slot arrays are sized for num_trees slots.
 static int queue_arm(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n, int slots) {
-  const int B = ctx->dp.B;
-  const size_t nB = (size_t)B;
-  EpQueueDev& q = ctx->q;
-  int rc;
-  for (hipEvent_t& e : ctx->q_ev)
-    if (!e) PB_TRY(ctx, hipEventCreate(&e));
-  if ((rc = ensure_drop_masks(ctx)) != POMCP_OK) return rc;
-  if (!q.fin_q) {   // (the last one allocated)
-    if ((rc = ctx->alloc(q.slot_q, nB)) != POMCP_OK || (rc = ctx->alloc(q.slot_ord, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(q.slot_start, nB)) != POMCP_OK || (rc = ctx->alloc(q.assign, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(q.state, 2)) != POMCP_OK || (rc = ctx->alloc(q.fin, nB)) != POMCP_OK ||
-        (rc = ctx->alloc(q.fin_q, nB)) != POMCP_OK)
-      return rc;
-  }
-  if (n > ctx->q_cap) {   // (an earlier, shorter queue stays allocated until the context goes)
-    ctx->q_cap = 0;
-    if ((rc = ctx->alloc(q.seeds, (size_t)n)) != POMCP_OK ||
-        (rc = ctx->alloc(q.rows, (size_t)n)) != POMCP_OK)
-      return rc;
-    ctx->q_cap = n;
-  }
-  q.drop = ctx->drop_masks;
-  q.acc_in = ctx->ep_acc ? ctx->acc.rec : nullptr;
-  q.acc = ctx->ep_acc ? ctx->acc.rec : nullptr;
-  q.n = n;
-  q.step = 0;
-  std::vector<int32_t> iota((size_t)slots), minus((size_t)slots, -1);
-  for (int b = 0; b < slots; ++b) iota[(size_t)b] = b;
-  const int32_t state[2] = {slots, 0};
-  if ((rc = ctx->upload(q.seeds, env_seeds, (size_t)n)) != POMCP_OK ||
-      (rc = ctx->upload(q.slot_q, iota.data(), (size_t)slots)) != POMCP_OK ||
-      (rc = ctx->upload(q.fin_q, minus.data(), (size_t)slots)) != POMCP_OK ||
-      (rc = ctx->upload(q.state, state, 2)) != POMCP_OK)
-    return rc;
-  PB_TRY(ctx, hipMemsetAsync(q.slot_ord, 0, sizeof(int32_t) * nB, ctx->stream));
-  PB_TRY(ctx, hipMemsetAsync(q.slot_start, 0, sizeof(int32_t) * nB, ctx->stream));
-  PB_TRY(ctx, hipMemsetAsync(q.rows, 0, sizeof(pomcp_episode_queue_row) * (size_t)n, ctx->stream));
-  PB_TRY(ctx, hipMemsetAsync(ctx->drop_masks, 0, sizeof(uint64_t) * (size_t)search_waves(B),
+  const int rc = ensure_drop_masks(ctx);
+  if (rc != POMCP_OK) return rc;
+  ctx->q.drop = ctx->drop_masks;
+  ctx->q.acc_in = ctx->ep_acc ? ctx->acc.rec : nullptr;
+  ctx->q.acc = ctx->ep_acc ? ctx->acc.rec : nullptr;
+  PB_TRY(ctx, hipMemsetAsync(ctx->drop_masks, 0, sizeof(uint64_t) * (size_t)search_waves(ctx->dp.B),
                              ctx->stream));
-  // (copied from the caller's and local memory: finish before returning)
-  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->q_ms[0] = ctx->q_ms[1] = 0.0;
-  ctx->q_active = true;
-  return POMCP_OK;
+  return ctx->arm_queue(ctx, env_seeds, n, slots, (size_t)ctx->dp.B);
 }
 
 int pomcp_episodes_queue_begin(pomcp_ctx* ctx, const uint64_t* env_seeds, int32_t n,
@@ -1552,13 +1425,6 @@ int pomcp_episodes_group_queue_begin(pomcp_ctx* ctx, int32_t group, const uint64
   return POMCP_OK;
 }
 
-static int queue_ready(pomcp_ctx* ctx, const char* what) {
-  if (!ctx->ep_active || !ctx->q_active)
-    return fail(ctx, POMCP_E_STATE, std::string(what) + ": pomcp_episodes_queue_begin first");
-  PB_TRY(ctx, hipSetDevice(ctx->device));
-  return POMCP_OK;
-}
-
 // The running queue's slots: the trees, or the groups of a queue of groups.
 static size_t queue_slots(const pomcp_ctx* ctx) {
   return (size_t)(ctx->gq_active ? ctx->dp.B / ctx->ep_group : ctx->dp.B);
@@ -1566,25 +1432,18 @@ static size_t queue_slots(const pomcp_ctx* ctx) {
 
 int pomcp_episodes_queue_rows(pomcp_ctx* ctx, pomcp_episode_queue_row* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  const int rc = queue_ready(ctx, "episodes_queue_rows");
-  return rc != POMCP_OK ? rc : ctx->fetch(out, (const pomcp_episode_queue_row*)ctx->q.rows,
-                                          (size_t)ctx->q.n);
+  return ctx->get_queue_rows(ctx, "pomcp", out);
 }
 
 int pomcp_episodes_queue_slots(pomcp_ctx* ctx, int32_t* out) {
   if (!ctx || !out) return POMCP_E_INVALID;
-  const int rc = queue_ready(ctx, "episodes_queue_slots");
-  return rc != POMCP_OK ? rc : ctx->fetch(out, (const int32_t*)ctx->q.slot_q, queue_slots(ctx));
+  return ctx->get_queue_slots(ctx, "pomcp", out, queue_slots(ctx));
 }
 
 int pomcp_episodes_queue_finished(pomcp_ctx* ctx, pomcp_episode_state* states_out,
                                   int32_t* queue_index_out) {
   if (!ctx || !states_out || !queue_index_out) return POMCP_E_INVALID;
-  int rc = queue_ready(ctx, "episodes_queue_finished");
-  if (rc != POMCP_OK) return rc;
-  if ((rc = ctx->fetch(queue_index_out, (const int32_t*)ctx->q.fin_q, queue_slots(ctx))) != POMCP_OK)
-    return rc;
-  return ctx->fetch(states_out, (const pomcp_episode_state*)ctx->q.fin, queue_slots(ctx));
+  return ctx->get_queue_finished(ctx, "pomcp", states_out, queue_index_out, queue_slots(ctx));
 }
 
 int pomcp_episodes_queue_finished_merged(pomcp_ctx* ctx, pomcp_merged_root* out) {
@@ -1598,8 +1457,7 @@ int pomcp_episodes_queue_finished_merged(pomcp_ctx* ctx, pomcp_merged_root* out)
 
 int pomcp_episodes_queue_timing(pomcp_ctx* ctx, double ms[2]) {
   if (!ctx || !ms) return POMCP_E_INVALID;
-  ms[0] = ctx->q_ms[0];
-  ms[1] = ctx->q_ms[1];
+  ctx->get_queue_timing(ms);
   return POMCP_OK;
 }
 

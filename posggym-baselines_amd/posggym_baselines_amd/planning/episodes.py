@@ -38,6 +38,9 @@ import math
 import time
 from typing import Callable, Dict, List, Optional
 
+import numpy as np
+import psutil
+
 from posggym_baselines_amd.planning.utils import PlanningStatTracker
 
 S_ENV_POLICY_BASE = 40   # philox.h S_ENV_POLICY_BASE: true agent i's random policy
@@ -68,6 +71,124 @@ def batch_episode_row(num, res, elapsed, search_ms, update_ms, steps, mem):
                    min_value=float(res["min_value_sum"]) / n,
                    max_value=float(res["max_value_sum"]) / n)
     return row
+
+
+# ----------------------------------------------------------------------------
+# The driver the batched entry points share (BatchedPOMCP.run_episodes /
+# run_episode_queue / run_planner_queue, BatchedINTMCP.run_episodes /
+# run_episode_queue): each checks the arguments only it has, then
+# episode_guards, play_batch and episode_rows.
+
+def check_until(until):
+    if until not in ("agent_done", "all_done"):
+        raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+
+
+def episode_guards(planner, what, until, max_steps=None):
+    """What every entry point checks before anything is launched: ``until``,
+    the model's ``spec.max_episode_steps`` (the default and upper limit of
+    ``max_steps``) and the planner's own arena sizing
+    (``planner._check_sized(what, max_steps)``); returns ``max_steps``."""
+    check_until(until)
+    spec = getattr(planner.engine.model, "spec", None)
+    limit = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
+    if limit < 1:
+        raise ValueError(f"{what} needs the model's spec.max_episode_steps")
+    max_steps = limit if max_steps is None else int(max_steps)
+    if not 1 <= max_steps <= limit:
+        raise ValueError(f"max_steps must be 1 to the model's max_episode_steps ({limit}), "
+                         f"not {max_steps}")
+    planner._check_sized(what, max_steps)
+    return max_steps
+
+
+def episode_population(planner, other_agents, known_ids=()):
+    """``other_agents`` as (the population's ids, its action distributions, each
+    policy's index among ``known_ids`` -- the policies the planners model -- or
+    -1); three ``None`` without a population."""
+    if other_agents is None:
+        return None, None, None
+    other_agents = list(other_agents)
+    probs = check_population(other_agents, planner.engine.A)
+    ids = [pol.policy_id for pol in other_agents]
+    known = list(known_ids or [])
+    return ids, probs, [known.index(i) if i in known else -1 for i in ids]
+
+
+def play_batch(planner, what, begin, fetch, slots, max_steps, on_step, entries=None,
+               noun="slots"):
+    """Begin a batch (``begin(pow_table)``: the population and the engine's
+    begin call), step its ``slots`` until none is live and ``fetch()`` its
+    records.  A batch plays ``max_steps`` steps at most; a queue of ``entries``
+    episodes ``entries * max_steps``, and one that has not drained by then
+    raises ``RuntimeError`` (``what``'s ``noun`` still playing).  Returns the
+    records and the batch's figures for ``episode_rows``: the wall-clock seconds
+    of all of this, the device search and update ms, the steps, the RSS (MiB)."""
+    engine = planner.engine
+    gamma = engine.config.discount
+    pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
+    step_cap = max_steps if entries is None else entries * max_steps
+    start = time.time()
+    begin(pow_table)
+    live, t = slots, 0
+    while live > 0 and t < step_cap:
+        live = engine.episodes_step(planner.num_sims)
+        if on_step is not None:
+            on_step(t, planner)
+        t += 1
+    if entries is not None and live > 0:
+        raise RuntimeError(f"{what}: {live} {noun} still playing after {t} steps")
+    res = fetch()
+    (upd_ms, search_ms, _), steps = engine.episodes_timing()
+    elapsed = time.time() - start
+    mem = psutil.Process().memory_info().rss / 1024**2
+    return res, (elapsed, search_ms, upd_ms, steps, mem)
+
+
+def belief_acc_columns(acc_stats, acc, acc_steps, max_steps):
+    """The ``BeliefStatTracker`` columns of a batch or a queue, every column for
+    all episodes at once: [(key, one value per episode)] in the tracker's key
+    order, from the device records ``acc`` (``pomcp_episode_belief_acc``) and,
+    with ``track_per_step``, the per-step table ``acc_steps`` (else ``None``).
+    A mean is NaN for an episode without a recorded step, a step's value NaN
+    past the episode's end; sum / count is one IEEE division, as Python's."""
+    from posggym_baselines_amd.planning.utils import BeliefStatTracker
+    cnt = acc["count"].astype(np.int64)
+    played = cnt > 0
+    t_idx = np.arange(max_steps)[None, :] < cnt[:, None]
+    columns = []
+    for key in BeliefStatTracker.get_stat_keys(acc_stats, acc_steps is not None, max_steps):
+        k, _, t = key[len("belief_"):].partition("_acc")
+        if not t:       # the episode's mean
+            v = 0.0 if k == "history" else acc[k + "_sum"] / np.maximum(cnt, 1)
+            col = np.where(played, v, np.nan)
+        else:           # step t's value ("_<t>")
+            t = int(t[1:])
+            v = 0.0 if k == "history" else acc_steps[:, t, ("state", "policy", "action").index(k)]
+            col = np.where(t_idx[:, t], v, np.nan)
+        columns.append((key, col.tolist()))
+    return columns
+
+
+def episode_rows(results, figures, write_row, *, queue=None, pop_ids=None, policy_index=None,
+                 acc_columns=()):
+    """One ``batch_episode_row`` per record of ``results`` (``num`` = its index)
+    with, in this order, ``slot`` / ``slot_order`` of the queue rows ``queue``,
+    ``other_policy_id`` = ``pop_ids[policy_index[i]]`` and ``acc_columns``;
+    ``write_row`` sees each row."""
+    rows = []
+    for i in range(len(results)):
+        row = batch_episode_row(i, results[i], *figures)
+        if queue is not None:
+            row.update(slot=int(queue["slot"][i]), slot_order=int(queue["slot_order"][i]))
+        if pop_ids is not None:
+            row["other_policy_id"] = pop_ids[int(policy_index[i])]
+        for key, col in acc_columns:
+            row[key] = col[i]
+        if write_row is not None:
+            write_row(row)
+        rows.append(row)
+    return rows
 
 
 class EpisodeEnvView:

@@ -49,6 +49,8 @@ from posggym_baselines_amd.envs import engine_model
 from posggym_baselines_amd import _native as N
 from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.engine import EngineBase
+from posggym_baselines_amd.planning.episodes import (episode_guards, episode_population,
+                                                     episode_rows, play_batch)
 from posggym_baselines_amd.planning.search_policy import RandomSearchPolicy
 from posggym_baselines_amd.planning.utils import PlanningStatTracker
 
@@ -669,31 +671,13 @@ class BatchedINTMCP:
         return self.engine.search(self.num_sims, fetch=fetch)
 
     # ------------------------------------------------------------ episodes
-    def _episode_guards(self, what, until, max_steps, other_agents):
-        """What ``run_episodes`` and ``run_episode_queue`` check before anything is
-        launched; returns (max_steps, the population's ids, its distributions)."""
-        if until not in ("agent_done", "all_done"):
-            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
-        spec = getattr(self.engine.model, "spec", None)
-        limit = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
-        if limit < 1:
-            raise ValueError(f"{what} needs the model's spec.max_episode_steps")
-        max_steps = limit if max_steps is None else int(max_steps)
-        if not 1 <= max_steps <= limit:
-            raise ValueError(f"max_steps must be 1 to the model's max_episode_steps ({limit}), "
-                             f"not {max_steps}")
+    def _check_sized(self, what, max_steps):
+        """``episode_guards``' sizing check: a pair's arenas hold the whole episode."""
         if self._planned_searches is not None and self._planned_searches < max_steps:
             raise ValueError(
                 f"{what} searches up to {max_steps} times per episode and a pair's arenas hold "
                 f"the whole episode: create the engine with BatchedINTMCP(..., searches={max_steps}) "
                 f"(this one was sized with searches={self._planned_searches})")
-        pop_ids = pop_probs = None
-        if other_agents is not None:
-            from posggym_baselines_amd.planning.episodes import check_population
-            other_agents = list(other_agents)
-            pop_probs = check_population(other_agents, self.engine.A)
-            pop_ids = [pol.policy_id for pol in other_agents]
-        return max_steps, pop_ids, pop_probs
 
     def run_episodes(self, env_seeds=None, *, until: str = "agent_done", max_steps=None,
                      other_agents=None, write_row=None, on_step=None):
@@ -737,38 +721,24 @@ class BatchedINTMCP:
         ``belief_acc`` / ``belief_states`` (``BeliefStatTracker`` has no parity
         target for an ``INTMCP``) and more than one GPU.
         """
-        from posggym_baselines_amd.planning.episodes import batch_episode_row
         B = self.num_pairs
         seeds = list(range(B)) if env_seeds is None else [int(s) for s in env_seeds]
         if len(seeds) != B:
             raise ValueError(f"env_seeds has {len(seeds)} entries for {B} pairs")
-        max_steps, pop_ids, pop_probs = self._episode_guards("run_episodes", until, max_steps,
-                                                             other_agents)
-        gamma = self.engine.config.discount
-        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
-        start = time.time()
-        self.engine.episodes_set_population(pop_probs)
-        self.engine.episodes_begin(seeds, pow_table, max_steps, until)
-        live, t = B, 0
-        while live > 0 and t < max_steps:
-            live = self.engine.episodes_step(self.num_sims)
-            if on_step is not None:
-                on_step(t, self)
-            t += 1
-        res = self.engine.episodes_results()   # (ends the batch: parked pairs restored)
-        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
-        elapsed = time.time() - start
-        mem = psutil.Process().memory_info().rss / 1024**2
-        pops = self.engine.episodes_pop_states() if pop_ids is not None else None
-        rows = []
-        for b in range(B):
-            row = batch_episode_row(b, res[b], elapsed, search_ms, upd_ms, steps, mem)
-            if pops is not None:
-                row["other_policy_id"] = pop_ids[int(pops["policy_index"][b])]
-            if write_row is not None:
-                write_row(row)
-            rows.append(row)
-        return rows
+        max_steps = episode_guards(self, "run_episodes", until, max_steps)
+        pop_ids, pop_probs, _ = episode_population(self, other_agents)
+        engine = self.engine
+
+        def begin(pow_table):
+            engine.episodes_set_population(pop_probs)
+            engine.episodes_begin(seeds, pow_table, max_steps, until)
+
+        # (episodes_results ends the batch: parked pairs restored)
+        res, figures = play_batch(self, "run_episodes", begin, engine.episodes_results, B,
+                                  max_steps, on_step)
+        pops = engine.episodes_pop_states() if pop_ids is not None else None
+        return episode_rows(res, figures, write_row, pop_ids=pop_ids,
+                            policy_index=None if pops is None else pops["policy_index"])
 
     def run_episode_queue(self, env_seeds, *, until: str = "agent_done", max_steps=None,
                           other_agents=None, write_row=None, on_step=None):
@@ -802,43 +772,29 @@ class BatchedINTMCP:
         in the step just played (their slots' ``episode_states()`` are the next
         episodes' by then).  Not offered: ``belief_acc`` / ``belief_states``.
         """
-        from posggym_baselines_amd.planning.episodes import batch_episode_row
         B = self.num_pairs
         seeds = [int(s) for s in env_seeds]
         N_ = len(seeds)
         if N_ < B:
             raise ValueError(f"run_episode_queue needs at least {B} env_seeds (one per pair), "
                              f"not {N_}")
-        max_steps, pop_ids, pop_probs = self._episode_guards("run_episode_queue", until, max_steps,
-                                                             other_agents)
-        gamma = self.engine.config.discount
-        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
-        start = time.time()
-        self.engine.episodes_set_population(pop_probs)
-        self.engine.episodes_queue_begin(seeds, pow_table, max_steps, until)
-        live, t = B, 0
-        while live > 0 and t < N_ * max_steps:
-            live = self.engine.episodes_step(self.num_sims)
-            if on_step is not None:
-                on_step(t, self)
-            t += 1
-        if live > 0:
-            raise RuntimeError(f"run_episode_queue: {live} slots still playing after {t} steps")
-        res = self.engine.episodes_queue_rows()
-        self.engine.episodes_results()   # (ends the batch: the retired slots' pairs restored)
-        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
-        elapsed = time.time() - start
-        mem = psutil.Process().memory_info().rss / 1024**2
-        rows = []
-        for i in range(N_):
-            row = batch_episode_row(i, res["res"][i], elapsed, search_ms, upd_ms, steps, mem)
-            row.update(slot=int(res["slot"][i]), slot_order=int(res["slot_order"][i]))
-            if pop_ids is not None:
-                row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
-            if write_row is not None:
-                write_row(row)
-            rows.append(row)
-        return rows
+        max_steps = episode_guards(self, "run_episode_queue", until, max_steps)
+        pop_ids, pop_probs, _ = episode_population(self, other_agents)
+        engine = self.engine
+
+        def begin(pow_table):
+            engine.episodes_set_population(pop_probs)
+            engine.episodes_queue_begin(seeds, pow_table, max_steps, until)
+
+        def fetch():
+            res = engine.episodes_queue_rows()
+            engine.episodes_results()   # (ends the batch: the retired slots' pairs restored)
+            return res
+
+        res, figures = play_batch(self, "run_episode_queue", begin, fetch, B, max_steps, on_step,
+                                  entries=N_)
+        return episode_rows(res["res"], figures, write_row, queue=res, pop_ids=pop_ids,
+                            policy_index=res["policy_index"])
 
     def episode_queue_slots(self):
         """The queue entry each slot of a running ``run_episode_queue`` is playing

@@ -44,6 +44,9 @@ from posggym_baselines_amd.envs import engine_model
 
 from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.engine import PomcpEngine, search_bytes
+from posggym_baselines_amd.planning.episodes import (belief_acc_columns, check_until,
+                                                     episode_guards, episode_population,
+                                                     episode_rows, play_batch)
 from posggym_baselines_amd.planning.other_policy import RandomOtherAgentPolicy
 from posggym_baselines_amd.planning.search_policy import RandomSearchPolicy, SearchPolicy
 from posggym_baselines_amd.planning.utils import PlanningStatTracker
@@ -534,9 +537,7 @@ class BatchedPOMCP:
         with ``belief_states`` or ``belief_acc`` (``ValueError``);
         ``run_planner_queue`` is the episode queue of such planners.
         """
-        from posggym_baselines_amd.planning.episodes import batch_episode_row
-        if until not in ("agent_done", "all_done"):
-            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        check_until(until)
         K = int(root_parallel)
         if K < 1 or self.num_trees % K:
             raise ValueError(f"root_parallel={root_parallel} does not divide num_trees = "
@@ -549,81 +550,30 @@ class BatchedPOMCP:
         if len(seeds) != B:
             raise ValueError(f"env_seeds has {len(seeds)} entries for {B} " +
                              ("trees" if K == 1 else f"planners of {K} replica trees"))
-        spec = getattr(self.engine.model, "spec", None)
-        max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
-        if max_steps < 1:
-            raise ValueError("run_episodes needs the model's spec.max_episode_steps")
-        if self._planned is not None:
-            searches, reroot = self._planned
-            if not reroot or searches < max_steps:
-                raise ValueError(
-                    f"run_episodes re-roots up to {max_steps} times per tree: create the engine "
-                    f"with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one was "
-                    f"sized with searches={searches}, reroot={reroot})")
+        max_steps = episode_guards(self, "run_episodes", until)
         acc_stats = self._belief_acc_stats(belief_acc)
         if track_per_step and not acc_stats:
             raise ValueError("track_per_step needs belief_acc")
-        pop_ids = pop_probs = mix = None
-        if other_agents is not None:
-            from posggym_baselines_amd.planning.episodes import check_population
-            other_agents = list(other_agents)
-            pop_probs = check_population(other_agents, self.engine.A)
-            pop_ids = [pol.policy_id for pol in other_agents]
-            known = self.other_policy_ids or []
-            mix = [known.index(i) if i in known else -1 for i in pop_ids]
-        gamma = self.engine.config.discount
-        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
-        start = time.time()
-        self.engine.episodes_set_population(pop_probs, mix)
-        self.engine.episodes_track_belief_acc(bool(acc_stats), track_per_step)
-        self.engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states,
-                                   group=K)
-        live, t = B, 0
-        while live > 0 and t < max_steps:
-            live = self.engine.episodes_step(self.num_sims)
-            if on_step is not None:
-                on_step(t, self)
-            t += 1
-        res = self.engine.episodes_results()
-        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
-        elapsed = time.time() - start
-        mem = psutil.Process().memory_info().rss / 1024**2
-        pops = self.engine.episodes_pop_states() if pop_ids is not None else None
-        acc = acc_steps = None
+        pop_ids, pop_probs, mix = episode_population(self, other_agents, self.other_policy_ids)
+        engine = self.engine
+
+        def begin(pow_table):
+            engine.episodes_set_population(pop_probs, mix)
+            engine.episodes_track_belief_acc(bool(acc_stats), track_per_step)
+            engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states,
+                                  group=K)
+
+        res, figures = play_batch(self, "run_episodes", begin, engine.episodes_results, B,
+                                  max_steps, on_step)
+        pops = engine.episodes_pop_states() if pop_ids is not None else None
+        acc_columns = ()
         if acc_stats:
-            from posggym_baselines_amd.planning.utils import BeliefStatTracker
-            acc = self.engine.episodes_belief_acc()
-            if track_per_step:
-                acc_steps = self.engine.episodes_belief_acc_steps(max_steps)
-            # every column for all trees at once: (key, one value per tree), in the
-            # tracker's key order; sum / count is one IEEE division, as Python's
-            cnt = acc["count"].astype(np.int64)
-            played = cnt > 0
-            t_idx = np.arange(max_steps)[None, :] < cnt[:, None]
-            acc_columns = []
-            for key in BeliefStatTracker.get_stat_keys(acc_stats, track_per_step, max_steps):
-                k, _, t = key[len("belief_"):].partition("_acc")
-                if not t:       # the episode's mean
-                    v = 0.0 if k == "history" else acc[k + "_sum"] / np.maximum(cnt, 1)
-                    col = np.where(played, v, np.nan)
-                else:           # step t's value ("_<t>"), NaN past the episode's end
-                    t = int(t[1:])
-                    v = 0.0 if k == "history" else \
-                        acc_steps[:, t, ("state", "policy", "action").index(k)]
-                    col = np.where(t_idx[:, t], v, np.nan)
-                acc_columns.append((key, col.tolist()))
-        rows = []
-        for b in range(B):
-            row = batch_episode_row(b, res[b], elapsed, search_ms, upd_ms, steps, mem)
-            if pops is not None:
-                row["other_policy_id"] = pop_ids[int(pops["policy_index"][b])]
-            if acc is not None:
-                for key, col in acc_columns:
-                    row[key] = col[b]
-            if write_row is not None:
-                write_row(row)
-            rows.append(row)
-        return rows
+            acc = engine.episodes_belief_acc()
+            acc_steps = engine.episodes_belief_acc_steps(max_steps) if track_per_step else None
+            acc_columns = belief_acc_columns(acc_stats, acc, acc_steps, max_steps)
+        return episode_rows(res, figures, write_row, pop_ids=pop_ids,
+                            policy_index=None if pops is None else pops["policy_index"],
+                            acc_columns=acc_columns)
 
     def run_episode_queue(self, env_seeds, *, until: str = "agent_done", other_agents=None,
                           belief_acc=False, belief_states: bool = False, write_row=None,
@@ -659,9 +609,7 @@ class BatchedPOMCP:
         ``root_parallel``: 1; a queue's slots are single trees (``ValueError``
         for groups of replicas: ``run_planner_queue`` is their queue).
         """
-        from posggym_baselines_amd.planning.episodes import batch_episode_row
-        if until not in ("agent_done", "all_done"):
-            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        check_until(until)
         if int(root_parallel) != 1:
             raise ValueError("run_episode_queue has no root_parallel groups: its slots are single "
                              "trees (run_planner_queue(root_parallel=K) is the queue of groups)")
@@ -671,67 +619,23 @@ class BatchedPOMCP:
         if N < B:
             raise ValueError(f"run_episode_queue needs at least {B} env_seeds (one per tree), "
                              f"not {N}")
-        spec = getattr(self.engine.model, "spec", None)
-        max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
-        if max_steps < 1:
-            raise ValueError("run_episode_queue needs the model's spec.max_episode_steps")
-        if self._planned is not None:
-            searches, reroot = self._planned
-            if not reroot or searches < max_steps:
-                raise ValueError(
-                    f"run_episode_queue re-roots up to {max_steps} times per episode: create the "
-                    f"engine with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one "
-                    f"was sized with searches={searches}, reroot={reroot})")
+        max_steps = episode_guards(self, "run_episode_queue", until)
         acc_stats = self._belief_acc_stats(belief_acc)
-        pop_ids = pop_probs = mix = None
-        if other_agents is not None:
-            from posggym_baselines_amd.planning.episodes import check_population
-            other_agents = list(other_agents)
-            pop_probs = check_population(other_agents, self.engine.A)
-            pop_ids = [pol.policy_id for pol in other_agents]
-            known = self.other_policy_ids or []
-            mix = [known.index(i) if i in known else -1 for i in pop_ids]
-        gamma = self.engine.config.discount
-        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
-        start = time.time()
-        self.engine.episodes_set_population(pop_probs, mix)
-        self.engine.episodes_track_belief_acc(bool(acc_stats), False)
-        self.engine.episodes_queue_begin(seeds, pow_table, max_steps, until,
-                                         track_states=belief_states)
-        live, t = B, 0
-        while live > 0 and t < N * max_steps:
-            live = self.engine.episodes_step(self.num_sims)
-            if on_step is not None:
-                on_step(t, self)
-            t += 1
-        if live > 0:
-            raise RuntimeError(f"run_episode_queue: {live} slots still playing after {t} steps")
-        res = self.engine.episodes_queue_rows()
-        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
-        elapsed = time.time() - start
-        mem = psutil.Process().memory_info().rss / 1024**2
-        acc_columns = []
-        if acc_stats:
-            from posggym_baselines_amd.planning.utils import BeliefStatTracker
-            acc = res["acc"]
-            cnt = acc["count"].astype(np.int64)
-            for key in BeliefStatTracker.get_stat_keys(acc_stats, False, max_steps):
-                k = key[len("belief_"):-len("_acc")]
-                # sum / count is one IEEE division, as Python's
-                v = 0.0 if k == "history" else acc[k + "_sum"] / np.maximum(cnt, 1)
-                acc_columns.append((key, np.where(cnt > 0, v, np.nan).tolist()))
-        rows = []
-        for i in range(N):
-            row = batch_episode_row(i, res["res"][i], elapsed, search_ms, upd_ms, steps, mem)
-            row.update(slot=int(res["slot"][i]), slot_order=int(res["slot_order"][i]))
-            if pop_ids is not None:
-                row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
-            for key, col in acc_columns:
-                row[key] = col[i]
-            if write_row is not None:
-                write_row(row)
-            rows.append(row)
-        return rows
+        pop_ids, pop_probs, mix = episode_population(self, other_agents, self.other_policy_ids)
+        engine = self.engine
+
+        def begin(pow_table):
+            engine.episodes_set_population(pop_probs, mix)
+            engine.episodes_track_belief_acc(bool(acc_stats), False)
+            engine.episodes_queue_begin(seeds, pow_table, max_steps, until,
+                                        track_states=belief_states)
+
+        res, figures = play_batch(self, "run_episode_queue", begin, engine.episodes_queue_rows, B,
+                                  max_steps, on_step, entries=N)
+        # (the per-episode means; there is no per-step table in queue mode)
+        acc_columns = belief_acc_columns(acc_stats, res["acc"], None, max_steps) if acc_stats else ()
+        return episode_rows(res["res"], figures, write_row, queue=res, pop_ids=pop_ids,
+                            policy_index=res["policy_index"], acc_columns=acc_columns)
 
     def run_planner_queue(self, env_seeds, *, root_parallel: int, until: str = "agent_done",
                           other_agents=None, write_row=None, on_step=None):
@@ -766,9 +670,7 @@ class BatchedPOMCP:
         merged record of the episodes that ended in the step just played.  Not
         combined with ``belief_states`` or ``belief_acc``.
         """
-        from posggym_baselines_amd.planning.episodes import batch_episode_row
-        if until not in ("agent_done", "all_done"):
-            raise ValueError(f"until must be 'agent_done' or 'all_done', not {until!r}")
+        check_until(until)
         K = int(root_parallel)
         if K < 2:
             raise ValueError(f"run_planner_queue needs root_parallel >= 2, not {root_parallel} "
@@ -782,53 +684,19 @@ class BatchedPOMCP:
         if N < G:
             raise ValueError(f"run_planner_queue needs at least {G} env_seeds (one per planner of "
                              f"{K} replica trees), not {N}")
-        spec = getattr(self.engine.model, "spec", None)
-        max_steps = int(spec.max_episode_steps) if spec is not None and spec.max_episode_steps else 0
-        if max_steps < 1:
-            raise ValueError("run_planner_queue needs the model's spec.max_episode_steps")
-        if self._planned is not None:
-            searches, reroot = self._planned
-            if not reroot or searches < max_steps:
-                raise ValueError(
-                    f"run_planner_queue re-roots up to {max_steps} times per episode: create the "
-                    f"engine with BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one "
-                    f"was sized with searches={searches}, reroot={reroot})")
-        pop_ids = pop_probs = mix = None
-        if other_agents is not None:
-            from posggym_baselines_amd.planning.episodes import check_population
-            other_agents = list(other_agents)
-            pop_probs = check_population(other_agents, self.engine.A)
-            pop_ids = [pol.policy_id for pol in other_agents]
-            known = self.other_policy_ids or []
-            mix = [known.index(i) if i in known else -1 for i in pop_ids]
-        gamma = self.engine.config.discount
-        pow_table = [gamma ** t for t in range(max_steps)]   # Python's own float ** int
-        start = time.time()
-        self.engine.episodes_set_population(pop_probs, mix)
-        self.engine.episodes_track_belief_acc(False, False)
-        self.engine.episodes_group_queue_begin(seeds, pow_table, max_steps, until, K)
-        live, t = G, 0
-        while live > 0 and t < N * max_steps:
-            live = self.engine.episodes_step(self.num_sims)
-            if on_step is not None:
-                on_step(t, self)
-            t += 1
-        if live > 0:
-            raise RuntimeError(f"run_planner_queue: {live} planners still playing after {t} steps")
-        res = self.engine.episodes_queue_rows()
-        (upd_ms, search_ms, _), steps = self.engine.episodes_timing()
-        elapsed = time.time() - start
-        mem = psutil.Process().memory_info().rss / 1024**2
-        rows = []
-        for i in range(N):
-            row = batch_episode_row(i, res["res"][i], elapsed, search_ms, upd_ms, steps, mem)
-            row.update(slot=int(res["slot"][i]), slot_order=int(res["slot_order"][i]))
-            if pop_ids is not None:
-                row["other_policy_id"] = pop_ids[int(res["policy_index"][i])]
-            if write_row is not None:
-                write_row(row)
-            rows.append(row)
-        return rows
+        max_steps = episode_guards(self, "run_planner_queue", until)
+        pop_ids, pop_probs, mix = episode_population(self, other_agents, self.other_policy_ids)
+        engine = self.engine
+
+        def begin(pow_table):
+            engine.episodes_set_population(pop_probs, mix)
+            engine.episodes_track_belief_acc(False, False)
+            engine.episodes_group_queue_begin(seeds, pow_table, max_steps, until, K)
+
+        res, figures = play_batch(self, "run_planner_queue", begin, engine.episodes_queue_rows, G,
+                                  max_steps, on_step, entries=N, noun="planners")
+        return episode_rows(res["res"], figures, write_row, queue=res, pop_ids=pop_ids,
+                            policy_index=res["policy_index"])
 
     def episode_queue_slots(self):
         """The queue entry each slot of a running ``run_episode_queue`` (each
@@ -848,6 +716,19 @@ class BatchedPOMCP:
         ended in the step just played; zeros for a group where none ended
         (``episode_merged_roots()`` is the next episode's by then)."""
         return self.engine.episodes_queue_finished_merged()
+
+    def _check_sized(self, what, max_steps):
+        """``episode_guards``' sizing check: the arenas planned by the constructor
+        hold ``max_steps`` searches with a re-root after each."""
+        if self._planned is None:
+            return
+        searches, reroot = self._planned
+        if not reroot or searches < max_steps:
+            per = "tree" if what == "run_episodes" else "episode"
+            raise ValueError(
+                f"{what} re-roots up to {max_steps} times per {per}: create the engine with "
+                f"BatchedPOMCP(..., searches={max_steps}, reroot=True) (this one was sized with "
+                f"searches={searches}, reroot={reroot})")
 
     def _belief_acc_stats(self, belief_acc):
         """``run_episodes``' ``belief_acc`` as the tracker's ``stats_to_track``
