@@ -102,6 +102,10 @@ class OraclePOMCP:
         self.root = self._new_obs_node(0, 0)
         self.last_action = None
         self.stats = {}
+        # test instrumentation only (never part of a record, digest or fixture):
+        # one (need, tries, accepted, rejected_total, parent_size) per
+        # _reinvigorate call; the caller clears it
+        self.reinvigorations = []
 
     # ---------------------------------------------------------------- minmax
     def _mm_update(self, v):                 # utils.py:29-32 (max()/min() keep first arg on ties)
@@ -183,6 +187,7 @@ class OraclePOMCP:
         """``mcts.py:651-700`` + ``belief.py:145-194`` (use_rejected_samples=True)."""
         n = self.cfg.num_particles + self.cfg.extra_particles - len(self.belief[node])
         if n <= 0:
+            self.reinvigorations.append((n, 0, 0, 0, len(self.belief[parent])))
             return
         pb = self.belief[parent]
         limit = self.cfg.reinvigoration_sample_limit_factor * n
@@ -201,6 +206,7 @@ class OraclePOMCP:
                 rejected.append(rec)
         if got < n:
             accepted.extend(rejected[: n - got])
+        self.reinvigorations.append((n, tries, got, len(rejected), len(pb)))
         self.belief[node].extend(accepted)
         del oid
 

@@ -40,6 +40,18 @@ CASES = {
     "pe_evader_ucb": ({}, 128, [(11, 11), (12, 12)], "0", 100, "PursuitEvasion-v1"),
     "pe_pursuer_pucb": ({"action_selection": "pucb"}, 96, [(13, 13)], "1", 100,
                         "PursuitEvasion-v1"),
+    # The rejection reinvigoration (mcts.py:651-700, belief.py:145-194) beyond one
+    # 64-try pass and off the default limit factor: 319 / 107 particles, short
+    # episodes.  The seeds were chosen with the oracle's recorder
+    # (OraclePOMCP.reinvigorations) so that the cases hold a try limit hit after
+    # more than 64 tries, more than 64 rejected particles filled in and more
+    # rejected particles than needed (tests/test_reinvigoration_fixtures.py)
+    "reinv_drv_ego1_f15": ({"search_time_limit": 3.0, "reinvigoration_sample_limit_factor": 1.5},
+                           64, [(3, 3), (6, 6)], "1", 8),
+    "reinv_pe_pursuer_f25": ({"search_time_limit": 1.0, "reinvigoration_sample_limit_factor": 2.5},
+                             64, [(1, 1), (3, 3)], "1", 8, "PursuitEvasion-v1"),
+    "reinv_pe_evader_f10": ({"search_time_limit": 1.0, "reinvigoration_sample_limit_factor": 1.0},
+                            48, [(2, 2)], "0", 8, "PursuitEvasion-v1"),
 }
 
 
@@ -231,6 +243,9 @@ POTMMCP_CASES = {
     "potmmcp_ucb_ego1": ({}, "B", 48, [(32, 32)], "1", 50, "Driving-v1"),
     "potmmcp_pe_pucb": ({"action_selection": "pucb"}, "PE", 48, [(33, 33)], "0", 100,
                         "PursuitEvasion-v1"),
+    # 107 particles: type-based particles reinvigorated over more than one pass
+    "potmmcp_pe_reinv": ({"action_selection": "pucb", "search_time_limit": 1.0}, "PE", 48,
+                         [(35, 35)], "0", 8, "PursuitEvasion-v1"),
 }
 # batched trees: the first step of trees 0..5 (keys (seed, k)), one episode each
 POTMMCP_TREES = ({"action_selection": "pucb"}, "A", 96, 34, 34, 6)
@@ -299,6 +314,10 @@ MCTS_CASES = {
     "mcts_pe_fs_ucb": ("POMCP", {}, "pe_fs", 48, [(47, 47)], "0", 100, "PursuitEvasion-v1"),
     "mcts_pe_mix_pucb": ("IPOMCP", {"action_selection": "pucb", "state_belief_only": False},
                          "pe_mix", 48, [(48, 48)], "1", 100, "PursuitEvasion-v1"),
+    # 107 particles: type-based particles reinvigorated over more than one pass
+    "mcts_pe_mix_reinv": ("IPOMCP", {"action_selection": "pucb", "state_belief_only": False,
+                                     "search_time_limit": 1.0},
+                          "pe_mix", 48, [(49, 49)], "1", 8, "PursuitEvasion-v1"),
 }
 
 

@@ -5,6 +5,11 @@ import os
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 EPISODE_CASES = ["c1_ucb", "c1_pucb", "uniform", "deep_ucb", "known_bounds", "ego1_ucb",
                  "large_first_step", "pe_evader_ucb", "pe_pursuer_pucb"]
+# the rejection reinvigoration beyond one 64-try pass, limit factors 1.5 / 2.5 /
+# 1.0 (make_golden.py CASES "reinv_*"; tests/test_reinvigoration_fixtures.py
+# asserts the path classes they hold): 8-step episodes
+REINVIGORATION_CASES = ["reinv_drv_ego1_f15", "reinv_pe_pursuer_f25", "reinv_pe_evader_f10"]
+EPISODE_CASES += REINVIGORATION_CASES
 
 
 def case_env(data):
@@ -14,6 +19,8 @@ def case_env(data):
 def case_max_steps(case, data):
     if case == "large_first_step":
         return 1
+    if case in REINVIGORATION_CASES:
+        return 8
     return 100 if case_env(data) == "PursuitEvasion-v1" else 50
 
 

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 MCTS_CASES = ["mcts_pomcp_fs_pucb", "mcts_pomcp_fs_ucb", "mcts_ipomcp_mix_pucb",
               "mcts_ipomcp_fs_mix_ucb_ego1", "mcts_fixed_other_pucb", "mcts_pe_fs_ucb",
-              "mcts_pe_mix_pucb"]
+              "mcts_pe_mix_pucb", "mcts_pe_mix_reinv"]
 
 
 def make_planner(data, cfg, model):

@@ -503,9 +503,15 @@ def test_wall_clock_episode_one_second():
 def test_reinvigoration_many_particles(time_limit):
     """The rejection reinvigoration (mcts.py:651-700, belief.py:145-194) at the
     reference's particle counts for 1 s and 20 s budgets (100 + 7 and 2000 + 125
-    particles, config.py:47-48): k_update runs 64 tries per pass (one per lane,
-    ballot-ranked accepts / rejects); beliefs equal the oracle's, insertion order
-    included (belief digests), over 3 real steps."""
+    particles, config.py:47-48), limit factor 4.0: k_update runs 64 tries per
+    pass, up to 34 passes here; beliefs equal the oracle's, insertion order
+    included (belief digests), over 3 real steps.  What it covers is the
+    all-accepted path over several passes from parents of at most 2,125
+    particles: in these Driving episodes every try is accepted (the oracle's
+    recorder shows accepted == need == tries in every call), so the try limit,
+    the rejected particles, their cap and the fill copy never take a
+    non-trivial branch.  Those paths, other limit factors and larger parents
+    are pinned by tests/test_gpu_reinvigoration.py."""
     from gpu_util import batched_episodes
     from oracle.run import oracle_episode
     cfg = dict(TEST_CFG, search_time_limit=time_limit)

@@ -12,7 +12,8 @@ from oracle.episode import fhex, run_episode
 
 pytestmark = pytest.mark.gpu
 
-POTMMCP_CASES = ["potmmcp_pucb", "potmmcp_ucb_ego1", "potmmcp_pe_pucb"]
+POTMMCP_CASES = ["potmmcp_pucb", "potmmcp_ucb_ego1", "potmmcp_pe_pucb",
+                 "potmmcp_pe_reinv"]
 
 
 def _policies(model, ego, spec):
