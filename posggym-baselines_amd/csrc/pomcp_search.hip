@@ -217,6 +217,39 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   uint32_t c_bel = h->ctr[0], c_sel = h->ctr[1], c_mod = h->ctr[2], c_a0 = h->ctr[3],
            c_a1 = h->ctr[4];
   const int log0 = n_log, blocks0 = n_blocks, nodes0 = n_nodes;
+  // The budgets of this launch as countdowns tested against a literal in the
+  // loop: the room left in the particle log (log_left) and in the block arena
+  // (blk_left) per lane, the simulations left (it_left, the loop's counter) per
+  // wave.  Compared with p.Np / p.Nb / num_sims themselves, the kernel
+  // arguments were loaded again inside the loop -- the compiler has no SGPR to
+  // keep them in -- each load followed by a wait that also drains the LDS queue
+  // (DESIGN.md §4 "Loop invariants").  n_log is derived from log_left at the
+  // end; n_blocks stays beside blk_left, it is the next block's index.
+#ifdef PB_NO_COUNTDOWN   // A/B builds: the compares against the kernel arguments
+#define PB_LOG_FULL() (n_log >= p.Np)
+#define PB_ARENA_FULL() (n_blocks >= p.Nb)
+#define PB_LOG_TAKE() (++n_log)
+#else
+  auto log_room = [&](int used) {
+    const int64_t room = p.Np - used;
+    return (int)(room < 0x7FFFFFFF ? room : 0x7FFFFFFF);
+  };
+#define PB_LOG_FULL() (log_left <= 0)
+#define PB_ARENA_FULL() (blk_left <= 0)
+#define PB_LOG_TAKE() (--log_left)
+  int log_left = log_room(n_log);
+  int blk_left = (int)(p.Nb - n_blocks < 0x7FFFFFFF ? p.Nb - n_blocks : 0x7FFFFFFF);
+#endif
+  // The FP64 kernel arguments the loop reads (UCB's c and fast-selection margin,
+  // the backup's discount).  DL = 1: held as VGPR pairs (vary()) -- that kernel
+  // loaded them again at every use (eight scalar loads in its loop) and has the
+  // registers to spare; the other kernels keep them in SGPRs.
+  auto loop_const = [&](double x) {
+    if constexpr (DL == 1)
+      return hilo_d(vary((uint32_t)__double2loint(x)), vary((uint32_t)__double2hiint(x)));
+    return x;
+  };
+  const double k_c = loop_const(p.c), k_margin = loop_const(p.sel_margin), k_discount = loop_const(p.discount);
   int c_rollout = 0, c_probes = 0, c_cut = 0, c_exact = 0;
 #ifdef POMCP_PHASE_TIMING
   uint64_t pt[16];
@@ -359,11 +392,14 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   // ObsNode.add_child for every action (mcts.py:279-281, 318-321): zeroed block
   // (TM: its prior line = the action_probs of prior code `code`)
   auto alloc_block = [&](int code) -> int {
-    if (n_blocks >= p.Nb) {
+    if (PB_ARENA_FULL()) {
       err = POMCP_E_ARENA;
       return -1;
     }
     const int b = n_blocks++;
+#ifndef PB_NO_COUNTDOWN
+    --blk_left;
+#endif
     uint4* d = reinterpret_cast<uint4*>(an + (int64_t)b * blk_bytes);
     for (int q = 0; q < blk_parts(A + 1); ++q) d[q] = make_uint4(0, 0, 0, 0);
     if constexpr (TM != 0) {
@@ -418,7 +454,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 #ifdef POMCP_ABLATE_SELECT   // ablation build only (tools/ablate.sh): no FP64 div / sqrt, breaks parity
 #pragma unroll
         for (int q = 0; q < A; ++q)
-          sc[q] = hilo_d(st[q].z, st[q].w) + p.c * log_n * (double)(int)st[q].x;
+          sc[q] = hilo_d(st[q].z, st[q].w) + k_c * log_n * (double)(int)st[q].x;
 #else
         // Fast scores: (v - min) * rcp(range) + c sqrt(log N) rsq(n), each
         // within a few ulp of the reference's (v - min) / range + c
@@ -431,7 +467,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
         // first of them wins in both).
         {
           const double rr = nz ? rcp_nr(range) : 1.0;
-          const double csl = p.c * sqrt_fast(log_n);
+          const double csl = k_c * sqrt_fast(log_n);
           double sf[A], mg[A];
 #pragma unroll
           for (int q = 0; q < A; ++q) {
@@ -459,7 +495,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 #pragma unroll
           for (int q = 0; q < A; ++q) {
             const bool same = st[q].x == sb.x && st[q].z == sb.z && st[q].w == sb.w;
-            amb |= q != af && !same && !(bf - sf[q] > p.sel_margin * (mg[q] + bm));
+            amb |= q != af && !same && !(bf - sf[q] > k_margin * (mg[q] + bm));
           }
           a = af;
           exact = amb;
@@ -473,7 +509,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
             const double v = hilo_d(st[q].z, st[q].w);
             const double nvq = nz ? (v - mm_min) / range : v;
             const int n = (int)st[q].x > 0 ? (int)st[q].x : 1;
-            sc[q] = nvq + p.c * sqrt(log_n / (double)n);
+            sc[q] = nvq + k_c * sqrt(log_n / (double)n);
           }
         }
 #endif
@@ -483,7 +519,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
         double cp[A];   // c * prior (exact: the same operations as the reference)
 #pragma unroll
         for (int q = 0; q < A; ++q)
-          cp[q] = p.c * ((TM != 0 ? ap[q] : 1.0 / (double)A) * (1.0 - p.pucb_f) + p.pucb_f * noise);
+          cp[q] = k_c * ((TM != 0 ? ap[q] : 1.0 / (double)A) * (1.0 - p.pucb_f) + p.pucb_f * noise);
 #ifndef POMCP_EXACT_SELECT
         {   // fast scores, the exact ones for near-ties (as UCB above); equal
             // statistics here include the prior (type-based priors differ)
@@ -518,7 +554,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 #pragma unroll
           for (int q = 0; q < A; ++q) {
             const bool same = st[q].x == sb.x && st[q].z == sb.z && st[q].w == sb.w && cp[q] == bp;
-            amb |= q != af && !same && !(bf - sf[q] > p.sel_margin * (mg[q] + bm));
+            amb |= q != af && !same && !(bf - sf[q] > k_margin * (mg[q] + bm));
           }
           a = af;
           exact = amb;
@@ -847,13 +883,22 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   // lanes in lockstep: the start and root level, then the levels below it
   // (one pass per depth while any lane still descends), the rollouts, the
   // backup.  A lane that has failed (or has no search) idles, masked.
+  // (a lane that starts a simulation has finished one in every iteration
+  // before: its `sims` is the iteration's index, so the wave-uniform it_left
+  // also tells whether a simulation follows this one)
+#ifdef PB_NO_COUNTDOWN
   for (int it = 0; it < num_sims; ++it) {
+    const bool more_sims = sims + 1 < num_sims;
+#else
+  for (int it_left = num_sims; it_left > 0; --it_left) {
+    const bool more_sims = it_left > 1;
+#endif
     PT_MARK(7);
     // ------------------------------------- start a simulation + the root level
     if (phase == TP_START) {
       {
         const uint4 pr = pf;                                     // belief.py:55
-        if (sims + 1 < num_sims) {
+        if (more_sims) {
 #ifdef POMCP_ABLATE_BELIEF   // ablation build only (tools/ablate.sh): no belief line per simulation
           pf.w += uniform_int(w_bel, (uint32_t)bsize) & 1u;
 #else
@@ -876,7 +921,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
             epol = tmt->meta_idx[pid][i];
           }
         }
-        if (0 > p.depth_limit || t > p.step_limit) {            // mcts.py:315
+        if ((DL > 0 ? false : 0 > p.depth_limit) || t > p.step_limit) {   // mcts.py:315 (DL > 0: the limit is DL)
           ret = 0.0;
           phase = TP_BACKUP;
         } else {
@@ -959,13 +1004,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
           if constexpr (TM != 0) {
             if (existed) prior_ema(rap, root_visits);
           }
-          if (err != 0 || n_log >= p.Np) {
+          if (err != 0 || PB_LOG_FULL()) {
             if (err == 0) err = POMCP_E_ARENA;
             phase = TP_DONE;
           } else {
             rec = LogRec{cid | ((uint32_t)lane << kIdBits), n0, n1};   // mcts.py:371
             app = true;
-            ++n_log;
+            PB_LOG_TAKE();
             r0_on = 1;
             r0_a = (uint32_t)a | ((uint32_t)done << 31);
             r0_vis = sa.x;
@@ -1027,7 +1072,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     append();   // the last level's record
     // ------------------------------------------------------ the rollout
     while (phase == TP_ROLL) {                               // mcts.py:414-450
-      if (!(rdepth <= p.depth_limit && t <= p.step_limit)) {
+      if (!(rdepth <= (DL > 0 ? DL : p.depth_limit) && t <= p.step_limit)) {
         phase = TP_BACKUP;
       } else {
         // the ego's rollout action: RandomSearchPolicy (search_policy.py:177) or,
@@ -1072,7 +1117,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
         constexpr int QC = decltype(qc)::value;
         const uint4 e0 = pe.e0, e1 = pe.e1, e2 = pe.e2;
         const double r = hilo_d(e0.z, e0.w);
-        gr = (e0.x >> 31) ? r : r + p.discount * gr;
+        gr = (e0.x >> 31) ? r : r + k_discount * gr;
         const int n = (int)e0.y + 1;
         const double value0 = hilo_d(e1.x, e1.y);
         const double total = hilo_d(e1.z, e1.w) + gr;
@@ -1136,7 +1181,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
       }
       if (r0_on) {   // the root level: statistics in LDS, totals in registers
         const int a = (int)(r0_a & 0x7FFFFFFFu);
-        gr = (r0_a >> 31) ? r0_r : r0_r + p.discount * gr;
+        gr = (r0_a >> 31) ? r0_r : r0_r + k_discount * gr;
         const int n = (int)r0_vis + 1;
         const double total = r0_tot + gr;
         const double delta = gr - r0_val;
@@ -1162,6 +1207,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 #endif
 
   q_flush();   // the last simulation's backup stores
+#ifndef PB_NO_COUNTDOWN
+  n_log = log0 + (log_room(log0) - log_left);
+#endif
   // ------------------------------------------------------------------ results
   {   // the wave's log length: every lane's appends of this launch
     uint32_t mine = valid ? (uint32_t)(n_log - log0) : 0u;
@@ -1322,6 +1370,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   so->n_cutoff = c_cut;
   so->n_exact_selects = c_exact;
 }
+#undef PB_LOG_FULL
+#undef PB_ARENA_FULL
+#undef PB_LOG_TAKE
 
 // Instantiated only in pomcp_search_tu.hip, the translation unit of its own
 // that k_search is compiled in (its scheduler flag, build.py); the C-ABI's

@@ -61,12 +61,27 @@
         const bool cutc = (D > 0 ? D + 1 > DL : depth + 1 > p.depth_limit) || t + 1 > p.step_limit;   // mcts.py:315
         c_cut += cutc ? 1 : 0;   // (stats: n_cutoff, and n_deferred when deferring)
         const bool skipc = TM == 0 && p.defer && cutc;
+        // An unrolled pass above the last one loads the slot line for every
+        // lane: a lane that skips reads the slot line of its own block and
+        // action (a valid address) and never uses it -- the skipc arm below
+        // comes first -- so neither the zero fill nor the exec-mask block
+        // round the loads is needed there.
+#ifdef PB_NO_UNCOND_SLOTS   // A/B builds: zero fill and conditional loads in every pass
+        constexpr bool kLoadAll = false;
+#else
+        constexpr bool kLoadAll = D > 0 && D < DL;
+#endif
         uint4 sl[kSlots];
-  #pragma unroll
-        for (int q = 0; q < kSlots; ++q) sl[q] = make_uint4(0, 0, 0, 0);
-        if (!skipc) {
+        if constexpr (kLoadAll) {
   #pragma unroll
           for (int q = 0; q < kSlots; ++q) sl[q] = ap[part_slot(a, q)];
+        } else {
+  #pragma unroll
+          for (int q = 0; q < kSlots; ++q) sl[q] = make_uint4(0, 0, 0, 0);
+          if (!skipc) {
+  #pragma unroll
+            for (int q = 0; q < kSlots; ++q) sl[q] = ap[part_slot(a, q)];
+          }
         }
         PT_MARK(3);
         append();   // the previous level's record, after this level's loads
@@ -78,8 +93,8 @@
         bool match = false;
         int ks = 0;
         // An unrolled pass above the last one looks up whatever skipc says (a
-        // skipping lane's result is not read: sl is zero, and the skipc arm
-        // below comes first): find_slot stays straight-line, and only a lane at
+        // skipping lane's result is not read: the skipc arm below comes
+        // first): find_slot stays straight-line, and only a lane at
         // its step limit skips there.  At the last pass (D = DL: skipc is
         // wave-uniform) and in the generic loop, where whole waves skip, the
         // condition stays and the lookup is jumped over.
@@ -134,13 +149,13 @@
           }
         }
         PT_MARK(13);
-        if (err != 0 || n_log >= p.Np || (D > 0 ? false : plen >= kMaxPath)) {
+        if (err != 0 || PB_LOG_FULL() || (D > 0 ? false : plen >= kMaxPath)) {
           if (err == 0) err = POMCP_E_ARENA;
           phase = TP_DONE;
         } else {
           rec = LogRec{cid | ((uint32_t)lane << kIdBits), n0, n1};   // mcts.py:371
           app = true;
-          ++n_log;
+          PB_LOG_TAKE();
           const uint32_t ba = ((uint32_t)blk << 3) | (uint32_t)a;   // blk < 2^26 / 30
           push_path(dc, PathEntry{
               make_uint4(ba | ((uint32_t)done << 31), sa.x, (uint32_t)__double2loint(r),

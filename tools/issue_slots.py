@@ -9,7 +9,12 @@ and counts, per section between consecutive ;@@MARK comments (in text order)
 and for the whole simulation loop (from the first mark 6 or 7, whichever the
 compiler placed first, to the last mark 4), the instructions by mnemonic prefix.
 
-usage: tools/issue_slots.py [--sections] [--dl 0 1 2 3] [--keep DIR]
+"s.load" counts the scalar memory loads (s_load_dword*: a kernel argument or
+a table word fetched again inside the loop, each followed by a wait that also
+drains the LDS queue) and "v.rdlane" the v_readlane_b32 (a scalar read back
+from an SGPR-spill lane), both part of their "s_" / "v.lane" columns.
+
+usage: tools/issue_slots.py [--sections] [--dl 0 1 2 3] [--keep DIR] [--asm DIR]
 """
 import argparse
 import os
@@ -24,8 +29,8 @@ sys.path.insert(0, os.path.join(ROOT, "posggym-baselines_amd"))
 from posggym_baselines_amd import build as B  # noqa: E402
 
 KERNEL = re.compile(r"^(_Z\w*k_searchI\w*?Env(Driving|PursuitEvasion)ELi1ELi\d+ELi256ELi0E\w*):")
-COLS = ("total", "v_", "v.f64", "v.cndmask", "v.cmp", "v.mov", "v.lane", "s_", "s.saveexec",
-        "s.branch", "s.waitcnt", "s.nop", "ds_", "global_", "other")
+COLS = ("total", "v_", "v.f64", "v.cndmask", "v.cmp", "v.mov", "v.lane", "v.rdlane", "s_", "s.load",
+        "s.saveexec", "s.branch", "s.waitcnt", "s.nop", "ds_", "global_", "other")
 
 
 def classify(mn: str, c: Counter) -> None:
@@ -42,8 +47,12 @@ def classify(mn: str, c: Counter) -> None:
             c["v.mov"] += 1
         if mn.startswith(("v_readlane", "v_writelane")):
             c["v.lane"] += 1
+        if mn.startswith("v_readlane"):
+            c["v.rdlane"] += 1
     elif mn.startswith("s_"):
         c["s_"] += 1
+        if mn.startswith("s_load_dword"):
+            c["s.load"] += 1
         if "saveexec" in mn:
             c["s.saveexec"] += 1
         if mn.startswith(("s_cbranch", "s_branch")):
@@ -118,7 +127,8 @@ def report(name, env, body, sections: bool):
         if mn:
             classify(mn, whole)
     print(f"  kernel: {whole['total']} instructions, lane moves {whole['v.lane']},"
-          f" saveexec in loop {loop['s.saveexec']}")
+          f" saveexec in loop {loop['s.saveexec']}, s_load in loop {loop['s.load']},"
+          f" v_readlane in loop {loop['v.rdlane']}")
 
 
 def main() -> None:
@@ -126,12 +136,14 @@ def main() -> None:
     ap.add_argument("--dl", type=int, nargs="*", default=[1, 2, 3, 0])
     ap.add_argument("--sections", action="store_true", help="one row per section between marks")
     ap.add_argument("--keep", help="keep the assembly files in this directory")
+    ap.add_argument("--asm", help="report the assembly files kept in this directory (no compile)")
     a = ap.parse_args()
-    d = a.keep or tempfile.mkdtemp()
+    d = a.asm or a.keep or tempfile.mkdtemp()
     os.makedirs(d, exist_ok=True)
     for dl in a.dl:
         out = os.path.join(d, f"search_dl{dl}.s")
-        compile_asm(dl, out)
+        if not a.asm:
+            compile_asm(dl, out)
         print(f"== DL = {dl}" + (" (generic)" if dl == 0 else ""))
         for name, env, body in kernels(out):
             report(name, env, body, a.sections)
