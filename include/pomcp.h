@@ -609,6 +609,58 @@ int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_ind
                           int32_t other_action, const double* other_pi, int32_t num_other,
                           double out[3]);
 
+/* ---- State-reactive population policies (ABI 7, additive) --------------------
+ * A policy of the population may act on the true state instead of drawing from
+ * a fixed distribution.  POMCP_POLICY_DRIVING_SHORTEST_PATH is the Driving-v1
+ * shortest-path agent (csrc/driving_policy.h drv_sp_action; the registry ids
+ * Driving-v1/A{0,40,60,80,100}Shortestpath-v0 of planning/policies.py):
+ *   param0  caution, 0..15: the rows of its observation window ahead in which
+ *           another vehicle makes it brake;
+ *   param1  vmax, 0..3: the speed it does not exceed while it has a choice.
+ * Its action is a function of the state before the joint action.  The word of
+ * the agent's policy stream is still taken at every step, so every counter
+ * advances as with a fixed distribution; the policy's pi row is not read (it
+ * must still be a valid distribution). */
+enum {
+  POMCP_POLICY_FIXED = 0,
+  POMCP_POLICY_DRIVING_SHORTEST_PATH = 1
+};
+typedef struct pomcp_policy_kinds {
+  int32_t kind[POMCP_MAX_TYPE_POLICIES];
+  int32_t param0[POMCP_MAX_TYPE_POLICIES];
+  int32_t param1[POMCP_MAX_TYPE_POLICIES];
+} pomcp_policy_kinds;
+/* The kinds of the population set last (copied; entries past its num_policies
+ * are not read); NULL: all fixed, which is also what every
+ * pomcp_episodes_set_population leaves.  POMCP_E_STATE without a population,
+ * POMCP_E_UNSUPPORTED for a reactive kind on a context that is not Driving-v1,
+ * POMCP_E_INVALID for an unknown kind or a parameter out of range. */
+int pomcp_episodes_set_population_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds);
+/* The kinds of a type-based context's other-agent policies (other_pi's order),
+ * valid after pomcp_set_type_policies, which resets them to fixed: a particle
+ * whose policy is reactive has the other agent act on the simulated state in
+ * the tree levels, the rollouts and the rejection reinvigoration.  The word of
+ * the action stream is still taken.  NULL: all fixed.  POMCP_E_STATE before
+ * pomcp_set_type_policies, POMCP_E_UNSUPPORTED for a reactive kind on a context
+ * that is not Driving-v1, POMCP_E_INVALID for a bad kind or parameter or with
+ * other_uniform. */
+int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds);
+
+/* Host twins.  out[i] = drv_sp_action(grid, own[i], other[i], caution, vmax)
+ * for n pairs of packed vehicle words. */
+int pomcp_host_driving_policy_actions(const pomcp_grid* grid, int64_t n, const uint32_t* own,
+                                      const uint32_t* other, int32_t caution, int32_t vmax,
+                                      int32_t* out);
+/* pomcp_host_episode_step_pop with the population's kinds (NULL: exactly that
+ * call). */
+int pomcp_host_episode_step_pop_kinds(int32_t env_id, const void* grid, int32_t ego,
+                                      const pomcp_episode_step_in* in, const double* pow_table,
+                                      int32_t max_steps, int32_t until,
+                                      const pomcp_episode_population* pop,
+                                      const pomcp_policy_kinds* kinds,
+                                      const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                                      pomcp_episode_step_out* out);
+
 /* ---- Episode queue (ABI 7, additive; csrc/pomcp_episode_queue.hip) ----------
  * n >= num_trees episodes on the context's num_trees slots: a tree whose
  * episode ends takes the next environment seed of a device-resident queue

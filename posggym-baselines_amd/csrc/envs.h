@@ -9,6 +9,9 @@
 //                              terminated-or-all-done flag (mcts.py:333-344)
 //   obs_key(m, ego, n0, n1)    the ego's packed observation
 //   done_of(ego, n0, n1)       step's done flag, from the next state alone
+//   policy_action(m, agent, s0, s1, kind, p0, p1) a state-reactive policy's
+//                              action for `agent` (pomcp_policy_kinds;
+//                              PursuitEvasion has no reactive kinds)
 //   sample_initial(m, draw, &s0, &s1)             model.sample_initial_state
 //   sample_agent_initial(m, ego, obs, draw, &s0, &s1)
 //                              model.sample_agent_initial_state (false: obs
@@ -20,6 +23,7 @@
 #include <stdint.h>
 
 #include "driving.h"
+#include "driving_policy.h"
 #include "driving_vec.h"
 #include "pursuit_evasion.h"
 
@@ -48,6 +52,11 @@ struct EnvDriving {
   __device__ static __forceinline__ uint64_t obs_key(const Model& m, int ego, uint32_t n0,
                                                      uint32_t n1) {
     return obs_key_vec(m, ego == 0 ? n0 : n1, ego == 0 ? n1 : n0);
+  }
+  __device__ static __forceinline__ uint32_t policy_action(const Model& m, int agent, uint32_t s0,
+                                                           uint32_t s1, int /*kind*/, int p0,
+                                                           int p1) {
+    return (uint32_t)drv_sp_action(m.g, agent == 0 ? s0 : s1, agent == 0 ? s1 : s0, p0, p1);
   }
   template <class Draw>
   __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
@@ -100,6 +109,10 @@ struct EnvPursuitEvasion {
   __device__ static __forceinline__ uint64_t obs_key(const Model& m, int ego, uint32_t n0,
                                                      uint32_t n1) {
     return pe_obs_key(m, ego, n0, n1);
+  }
+  __device__ static __forceinline__ uint32_t policy_action(const Model&, int, uint32_t, uint32_t,
+                                                           int, int, int) {
+    return 0u;   // (no reactive kinds: pomcp_set_type_policy_kinds refuses them)
   }
   template <class Draw>
   __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {

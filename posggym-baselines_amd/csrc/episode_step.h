@@ -20,12 +20,15 @@
 // utils/agent_env_wrapper.py:8-27) and the step turns the same word of the
 // agent's stream into an action as CPython's random.choices does
 // (PopulationAgents, planning/episodes.py).  A null population is the uniform
-// agent, draw for draw.
+// agent, draw for draw.  A member of a reactive kind (pomcp_policy_kinds)
+// acts on the true state before the joint action instead (E::policy_action);
+// the word is still taken, so every counter advances as for a fixed member.
 #ifndef PB_EPISODE_STEP_H_
 #define PB_EPISODE_STEP_H_
 #include <stdint.h>
 
 #include "driving.h"
+#include "driving_policy.h"
 #include "philox.h"
 #include "pursuit_evasion.h"
 #include "../../include/pomcp.h"
@@ -59,6 +62,12 @@ struct EpDriving {
   PB_HD static uint64_t obs_key(const Model& m, int agent, uint32_t n0, uint32_t n1) {
     return agent == 0 ? obs_key_fast(m, n0, n1) : obs_key_fast(m, n1, n0);
   }
+  PB_HD static bool has_kind(int kind) { return kind == POMCP_POLICY_DRIVING_SHORTEST_PATH; }
+  // the action of `agent` under a reactive kind in the state (s0, s1)
+  PB_HD static int policy_action(const Model& m, int agent, uint32_t s0, uint32_t s1, int /*kind*/,
+                                 int p0, int p1) {
+    return drv_sp_action(m.g, agent == 0 ? s0 : s1, agent == 0 ? s1 : s0, p0, p1);
+  }
 };
 
 struct EpPursuitEvasion {
@@ -80,6 +89,9 @@ struct EpPursuitEvasion {
   PB_HD static uint64_t obs_key(const Model& m, int agent, uint32_t n0, uint32_t n1) {
     return pe_obs_key(m, agent, n0, n1);
   }
+  // (no reactive kinds: a population with one is refused before it gets here)
+  PB_HD static bool has_kind(int /*kind*/) { return false; }
+  PB_HD static int policy_action(const Model&, int, uint32_t, uint32_t, int, int, int) { return 0; }
 };
 
 // A population's draw tables: random.choices' cumulative weights
@@ -90,6 +102,10 @@ struct EpPopTables {
   double cum[POMCP_MAX_TYPE_POLICIES][POMCP_MAX_ACTIONS];
   double tot[POMCP_MAX_TYPE_POLICIES];
   int32_t mix[POMCP_MAX_TYPE_POLICIES];
+  // pomcp_policy_kinds: POMCP_POLICY_FIXED draws from cum / tot, a reactive
+  // kind acts by E::policy_action(kind, p0, p1)
+  int32_t kind[POMCP_MAX_TYPE_POLICIES];
+  int32_t p0[POMCP_MAX_TYPE_POLICIES], p1[POMCP_MAX_TYPE_POLICIES];
 };
 
 // false: not 1..8 policies, a negative (or NaN) probability, or a zero sum.
@@ -111,6 +127,27 @@ inline bool ep_pop_tables(const pomcp_episode_population& p, int A, EpPopTables*
     t->mix[k] = p.mixture_index[k];
   }
   return true;
+}
+
+// The kinds of a population's policies into its tables (null: all fixed).
+// POMCP_E_UNSUPPORTED: a reactive kind the environment E does not have;
+// POMCP_E_INVALID: an unknown kind or a parameter out of range.
+template <class E>
+inline int ep_pop_kinds(const pomcp_policy_kinds* kinds, EpPopTables* t) {
+  for (int k = 0; k < POMCP_MAX_TYPE_POLICIES; ++k) t->kind[k] = t->p0[k] = t->p1[k] = 0;
+  if (kinds == nullptr) return POMCP_OK;
+  for (int k = 0; k < t->n; ++k) {
+    if (!drv_policy_kind_ok(kinds->kind[k], kinds->param0[k], kinds->param1[k]))
+      return POMCP_E_INVALID;
+    if (kinds->kind[k] != POMCP_POLICY_FIXED && !E::has_kind(kinds->kind[k]))
+      return POMCP_E_UNSUPPORTED;
+  }
+  for (int k = 0; k < t->n; ++k) {
+    t->kind[k] = kinds->kind[k];
+    t->p0[k] = kinds->param0[k];
+    t->p1[k] = kinds->param1[k];
+  }
+  return POMCP_OK;
 }
 
 // random.choices(range(n), weights): bisect_right(cum, x, 0, n - 1) for
@@ -224,7 +261,10 @@ PB_HD void episode_step(const typename E::Model& m, int ego, const pomcp_episode
   int a_oth;
   if (pop != nullptr) {
     const int k = policy_index >= 0 && policy_index < pop->n ? policy_index : 0;
-    a_oth = ep_choice(pop->cum[k], pop->tot[k], (int)E::kA, w_oth);
+    if (pop->kind[k] != POMCP_POLICY_FIXED)
+      a_oth = E::policy_action(m, other, s.v0, s.v1, pop->kind[k], pop->p0[k], pop->p1[k]);
+    else
+      a_oth = ep_choice(pop->cum[k], pop->tot[k], (int)E::kA, w_oth);
   } else {
     a_oth = (int)uniform_int(w_oth, E::kA);
   }

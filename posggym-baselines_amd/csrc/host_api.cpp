@@ -25,6 +25,7 @@
 
 #include "belief_stats.h"
 #include "driving.h"
+#include "driving_policy.h"
 #include "episode_group.h"
 #include "episode_group_queue.h"
 #include "episode_queue.h"
@@ -106,6 +107,18 @@ int pomcp_driving_obs(const pomcp_grid* g, const uint32_t state[2], uint64_t obs
   make_model(g, &m);
   obs_keys_out[0] = obs_key_fast(m, state[0], state[1]);
   obs_keys_out[1] = obs_key_fast(m, state[1], state[0]);
+  return POMCP_OK;
+}
+
+// The shortest-path agents' rule (driving_policy.h), the code the kernels run.
+int pomcp_host_driving_policy_actions(const pomcp_grid* g, int64_t n, const uint32_t* own,
+                                      const uint32_t* other, int32_t caution, int32_t vmax,
+                                      int32_t* out) {
+  if (!g || n < 0 || (n > 0 && (!own || !other || !out)) ||
+      !drv_policy_kind_ok(POMCP_POLICY_DRIVING_SHORTEST_PATH, caution, vmax))
+    return POMCP_E_INVALID;
+  const DrvGrid& gg = *reinterpret_cast<const DrvGrid*>(g);
+  for (int64_t i = 0; i < n; ++i) out[i] = drv_sp_action(gg, own[i], other[i], caution, vmax);
   return POMCP_OK;
 }
 
@@ -281,14 +294,16 @@ int pomcp_host_episode_reset_pop(int32_t env_id, const void* grid, int32_t ego, 
   return POMCP_OK;
 }
 
-int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
-                                const pomcp_episode_step_in* in, const double* pow_table,
-                                int32_t max_steps, int32_t until,
-                                const pomcp_episode_population* pop,
-                                const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
-                                pomcp_episode_step_out* out) {
+// (kinds: the population's pomcp_policy_kinds, null for all fixed)
+int pomcp_host_episode_step_pop_kinds(int32_t env_id, const void* grid, int32_t ego,
+                                      const pomcp_episode_step_in* in, const double* pow_table,
+                                      int32_t max_steps, int32_t until,
+                                      const pomcp_episode_population* pop,
+                                      const pomcp_policy_kinds* kinds,
+                                      const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                                      pomcp_episode_step_out* out) {
   if (!episode_env_ok(env_id, grid, ego) || !in || !pow_table || !st || !out || max_steps < 1 ||
-      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
+      (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE) || (kinds && !pop))
     return POMCP_E_INVALID;
   EpPopTables t;
   if (pop) {
@@ -296,6 +311,9 @@ int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
                                                                 : (int)EpPursuitEvasion::kA, &t) ||
         ps->policy_index < 0 || ps->policy_index >= t.n)
       return POMCP_E_INVALID;
+    const int rc = env_id == POMCP_ENV_DRIVING ? ep_pop_kinds<EpDriving>(kinds, &t)
+                                               : ep_pop_kinds<EpPursuitEvasion>(kinds, &t);
+    if (rc != POMCP_OK) return rc;
   }
   const EpPopTables* tp = pop ? &t : nullptr;
   const int k = pop ? ps->policy_index : -1;
@@ -309,6 +327,16 @@ int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
     episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
   }
   return POMCP_OK;
+}
+
+int pomcp_host_episode_step_pop(int32_t env_id, const void* grid, int32_t ego,
+                                const pomcp_episode_step_in* in, const double* pow_table,
+                                int32_t max_steps, int32_t until,
+                                const pomcp_episode_population* pop,
+                                const pomcp_episode_pop_state* ps, pomcp_episode_state* st,
+                                pomcp_episode_step_out* out) {
+  return pomcp_host_episode_step_pop_kinds(env_id, grid, ego, in, pow_table, max_steps, until, pop,
+                                           nullptr, ps, st, out);
 }
 
 // The per-group decision of k_group_episode_step (pomcp_episode_group.hip) on

@@ -77,6 +77,23 @@ struct __attribute__((visibility("hidden"))) EpisodeHost {
     return POMCP_OK;
   }
 
+  // The kinds of that population's policies (null: all fixed, as set_population
+  // leaves them); E: the episode environment of the context.
+  template <class E>
+  int set_population_kinds(HostCtx* ctx, const pomcp_policy_kinds* kinds) {
+    if (!ep_pop_set)
+      return fail(ctx, POMCP_E_STATE, "episodes_set_population_kinds: episodes_set_population first");
+    EpPopTables t = host_pop;
+    const int rc = ep_pop_kinds<E>(kinds, &t);
+    if (rc == POMCP_E_UNSUPPORTED)
+      return fail(ctx, rc, "episodes_set_population_kinds: the environment has no such reactive "
+                           "policy kind (Driving-v1 has the shortest-path agents)");
+    if (rc != POMCP_OK)
+      return fail(ctx, rc, "episodes_set_population_kinds: kind 0..1, caution 0..15, vmax 0..3");
+    host_pop = t;
+    return POMCP_OK;
+  }
+
   // What a begin needs before the layer's reset: the events, the records of
   // `slots` trees or pairs (the counts of `nparts` step workgroups), the power
   // table and the population's device copy.  The layer's own records follow.

@@ -787,6 +787,33 @@ int pomcp_set_type_policies(pomcp_ctx* ctx, const pomcp_type_policies* tp) {
   return POMCP_OK;
 }
 
+int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!ctx->dp.tm || !ctx->tm_set)
+    return fail(ctx, POMCP_E_STATE, "set_type_policy_kinds: pomcp_set_type_policies first");
+  TmTables t = ctx->host_tm;
+  for (int j = 0; j < kTmMax; ++j) t.oth_kind[j] = t.oth_p0[j] = t.oth_p1[j] = 0;
+  for (int j = 0; kinds && j < t.n_other; ++j) {
+    if (!drv_policy_kind_ok(kinds->kind[j], kinds->param0[j], kinds->param1[j]))
+      return fail(ctx, POMCP_E_INVALID, "set_type_policy_kinds: kind 0..1, caution 0..15, vmax 0..3");
+    if (kinds->kind[j] == POMCP_POLICY_FIXED) continue;
+    if (ctx->dp.env != POMCP_ENV_DRIVING)
+      return fail(ctx, POMCP_E_UNSUPPORTED, "set_type_policy_kinds: the environment has no such "
+                                            "reactive policy kind");
+    if (t.other_uniform)
+      return fail(ctx, POMCP_E_INVALID, "set_type_policy_kinds: other_uniform draws no policy");
+    t.oth_kind[j] = kinds->kind[j];
+    t.oth_p0[j] = kinds->param0[j];
+    t.oth_p1[j] = kinds->param1[j];
+  }
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_tm = t;
+  const int rc = ctx->upload(ctx->dp.tmt, &ctx->host_tm, 1);
+  if (rc != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
 int pomcp_get_root_prior(pomcp_ctx* ctx, int32_t tree, double* out) {
   if (!ctx || !out || tree < 0 || tree >= ctx->dp.B) return POMCP_E_INVALID;
   if (!ctx->dp.tm) return fail(ctx, POMCP_E_STATE, "get_root_prior: context is not type_based");
@@ -1310,6 +1337,13 @@ int pomcp_episodes_belief_stats(pomcp_ctx* ctx, pomcp_belief_counts* out) {
 int pomcp_episodes_set_population(pomcp_ctx* ctx, const pomcp_episode_population* pop) {
   if (!ctx) return POMCP_E_INVALID;
   return ctx->set_population(ctx, pop, ctx->dp.A, true);   // from the next pomcp_episodes_begin on
+}
+
+int pomcp_episodes_set_population_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds) {
+  if (!ctx) return POMCP_E_INVALID;
+  return ctx->dp.env == POMCP_ENV_DRIVING
+             ? ctx->set_population_kinds<EpDriving>(ctx, kinds)
+             : ctx->set_population_kinds<EpPursuitEvasion>(ctx, kinds);
 }
 
 int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out) {

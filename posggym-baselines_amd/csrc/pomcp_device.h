@@ -168,6 +168,11 @@ struct TmTables {
   double meta_tot[kTmMax];
   int32_t meta_idx[kTmMax][kTmMax];     // ego policy of meta_policy[j]'s i-th key
   int32_t meta_len[kTmMax];
+  // pomcp_policy_kinds of the other-agent policies (pomcp_set_type_policy_kinds):
+  // POMCP_POLICY_FIXED draws from oth_cum / oth_tot, a reactive kind acts by
+  // Env::policy_action(kind, p0, p1) on the running state; the word is taken
+  // either way
+  int32_t oth_kind[kTmMax], oth_p0[kTmMax], oth_p1[kTmMax];
 };
 // random.choices(population, weights): bisect_right(cum, x, 0, n - 1) for
 // x = random() * total, as CPython computes it (a linear scan: n <= 8).

@@ -553,10 +553,15 @@ __global__ __launch_bounds__(256) void k_update(DevParams p) {
                 const uint4 hp = *T.rbel(uniform_int(wb, (uint32_t)T.bsize));
                 // the other agent's action: uniform, or (type-based) by the
                 // particle's policy (OtherAgentMixturePolicy.sample_action)
-                const uint32_t ao = p.tm && !p.tmt->other_uniform
-                                        ? (uint32_t)tm_choice(p.tmt->oth_cum[hp.w], p.tmt->oth_tot[hp.w],
-                                                              p.A, wa)
-                                        : uniform_int(wa, (uint32_t)p.A);
+                // (a state-reactive policy acts on the particle's state)
+                uint32_t ao;
+                if (!p.tm || p.tmt->other_uniform)
+                  ao = uniform_int(wa, (uint32_t)p.A);
+                else if (p.tmt->oth_kind[hp.w] != POMCP_POLICY_FIXED)
+                  ao = Env::policy_action(sm, p.other, hp.y, hp.z, p.tmt->oth_kind[hp.w],
+                                          p.tmt->oth_p0[hp.w], p.tmt->oth_p1[hp.w]);
+                else
+                  ao = (uint32_t)tm_choice(p.tmt->oth_cum[hp.w], p.tmt->oth_tot[hp.w], p.A, wa);
                 uint32_t n0, n1;
                 double r;
                 int done;

@@ -366,8 +366,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     }
   };
   // the other agent's action (mcts.py:602-615): uniform (RandomOtherAgentPolicy)
-  // or, TM, by its particle's policy (OtherAgentMixturePolicy.sample_action)
-  auto take_oth = [&]() -> uint32_t {
+  // or, TM, by its particle's policy (OtherAgentMixturePolicy.sample_action);
+  // (v0, v1): the simulation's state, which a state-reactive policy acts on
+  auto take_oth = [&](uint32_t v0, uint32_t v1) -> uint32_t {
     const bool o0 = p.other == 0;
     const uint32_t j = o0 ? c_a0 : c_a1;
     const uint32_t w = blk_word(1, j - o_base, (uint32_t)S_ACT_BASE + (o0 ? 0u : 1u), j);
@@ -375,6 +376,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     c_a1 += o0 ? 0u : 1u;
     if constexpr (TM != 0) {
       if (tmt->other_uniform) return uniform_int(w, (uint32_t)A);
+      // a state-reactive policy: by the running state (divergent per lane, no barrier)
+      if (tmt->oth_kind[pid] != POMCP_POLICY_FIXED)
+        return Env::policy_action(sm, p.other, v0, v1, tmt->oth_kind[pid], tmt->oth_p0[pid],
+                                  tmt->oth_p1[pid]);
       return (uint32_t)tm_choice(tmt->oth_cum[pid], tmt->oth_tot[pid], A, w);
     } else {
       return uniform_int(w, (uint32_t)A);
@@ -926,7 +931,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
           phase = TP_BACKUP;
         } else {
           const uint32_t j = take_mod(2);
-          const uint32_t ao = take_oth();
+          const uint32_t ao = take_oth(s0, s1);
           uint4 st[kMaxA];
 #pragma unroll
           for (int q = 0; q < kMaxA; ++q) st[q] = q < A ? rc[rc_stats(q)][lid] : make_uint4(0, 0, 0, 0);
@@ -1084,7 +1089,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
                                 : (uint32_t)tm_choice(tmt->ego_cum[epol], tmt->ego_tot[epol], A, aw);
         else ae = uniform_int(aw, (uint32_t)A);
         const uint32_t j = take_mod(2);
-        const uint32_t ao = take_oth();                       // other_policy.py:151
+        const uint32_t ao = take_oth(s0, s1);                       // other_policy.py:151
         uint32_t n0, n1;
         double r;
         int dn;

@@ -261,6 +261,18 @@ class PomcpEpisodePopState(C.Structure):
     ]
 
 
+POLICY_FIXED, POLICY_DRIVING_SHORTEST_PATH = 0, 1   # pomcp_policy_kinds.kind
+
+
+class PomcpPolicyKinds(C.Structure):
+    """``pomcp_policy_kinds`` (include/pomcp.h)."""
+    _fields_ = [
+        ("kind", C.c_int32 * POMCP_MAX_TYPE_POLICIES),
+        ("param0", C.c_int32 * POMCP_MAX_TYPE_POLICIES),
+        ("param1", C.c_int32 * POMCP_MAX_TYPE_POLICIES),
+    ]
+
+
 class PomcpEpisodeBeliefAcc(C.Structure):
     """``pomcp_episode_belief_acc`` (include/pomcp.h)."""
     _fields_ = [
@@ -398,6 +410,15 @@ SIGNATURES = [
       C.POINTER(PomcpEpisodeState), C.POINTER(PomcpEpisodeStepOut)]),
     ("pomcp_host_belief_acc", C.c_int,
      [C.POINTER(PomcpBeliefCounts), C.c_int32, C.c_int32, _PD, C.c_int32, _PD]),
+    ("pomcp_episodes_set_population_kinds", C.c_int, [_CTX, C.POINTER(PomcpPolicyKinds)]),
+    ("pomcp_set_type_policy_kinds", C.c_int, [_CTX, C.POINTER(PomcpPolicyKinds)]),
+    ("pomcp_host_driving_policy_actions", C.c_int,
+     [C.POINTER(PomcpGrid), C.c_int64, _PU32, _PU32, C.c_int32, C.c_int32, _P32]),
+    ("pomcp_host_episode_step_pop_kinds", C.c_int,
+     [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PomcpEpisodeStepIn), _PD, C.c_int32, C.c_int32,
+      C.POINTER(PomcpEpisodePopulation), C.POINTER(PomcpPolicyKinds),
+      C.POINTER(PomcpEpisodePopState), C.POINTER(PomcpEpisodeState),
+      C.POINTER(PomcpEpisodeStepOut)]),
     ("pomcp_episodes_queue_begin", C.c_int, [_CTX, _PU64, C.c_int32, _PD, C.c_int32, C.c_int32]),
     ("pomcp_episodes_queue_rows", C.c_int, [_CTX, C.POINTER(PomcpEpisodeQueueRow)]),
     ("pomcp_episodes_queue_slots", C.c_int, [_CTX, _P32]),

@@ -336,6 +336,23 @@ class EngineBase:
         self._check(self._fn("episodes_set_population")(self._ctx, C.byref(pop)),
                     "episodes_set_population")
 
+    def episodes_set_population_kinds(self, kinds=None):
+        """The kinds of the population set last
+        (``pomcp_episodes_set_population_kinds``): per policy ``(kind, param0,
+        param1)`` of ``pomcp_policy_kinds``; ``None``: all fixed distributions,
+        which is also what every ``episodes_set_population`` leaves."""
+        if kinds is None:
+            self._check(self._fn("episodes_set_population_kinds")(self._ctx, None),
+                        "episodes_set_population_kinds")
+            return
+        if not 1 <= len(kinds) <= N.POMCP_MAX_TYPE_POLICIES:
+            raise ValueError(f"a population has 1 to {N.POMCP_MAX_TYPE_POLICIES} policies")
+        rec = N.PomcpPolicyKinds()
+        for k, (kind, p0, p1) in enumerate(kinds):
+            rec.kind[k], rec.param0[k], rec.param1[k] = int(kind), int(p0), int(p1)
+        self._check(self._fn("episodes_set_population_kinds")(self._ctx, C.byref(rec)),
+                    "episodes_set_population_kinds")
+
     def episodes_pop_states(self):
         """Every tree's ``pomcp_episode_pop_state``: the policy index its episode
         drew from the population (-1 without one) and that policy's mixture index."""
@@ -434,6 +451,15 @@ class PomcpEngine(EngineBase):
         if type_policies is not None:
             self._check(lib.pomcp_set_type_policies(ctx, C.byref(type_policies)),
                         "set_type_policies")
+        # the other-agent policies' kinds ((kind, param0, param1) each; the table
+        # builders of ipomcp.py / potmmcp.py attach them): state-reactive ones
+        kinds = getattr(type_policies, "other_kinds", None)
+        self.other_reactive = bool(kinds)
+        if kinds:
+            rec = N.PomcpPolicyKinds()
+            for k, (kind, p0, p1) in enumerate(kinds):
+                rec.kind[k], rec.param0[k], rec.param1[k] = int(kind), int(p0), int(p1)
+            self._check(lib.pomcp_set_type_policy_kinds(ctx, C.byref(rec)), "set_type_policy_kinds")
         # search kernel override (tests / benchmarks): POMCP_SEARCH_KERNEL=lane|wave.
         # A type-based (POTMMCP) context has only the lane kernel: the process-wide
         # override does not apply to it (an explicit set_search_kernel still raises)

@@ -24,7 +24,9 @@ With ``other_agents=[FixedDistributionPolicy, ...]`` the other agent of every
 episode is drawn from that test population instead (``UniformOtherAgentFn``,
 ``posggym_baselines/utils/agent_env_wrapper.py:8-27``: ``model.rng.choice(ids)``
 at every reset; ``PopulationAgents`` below), and the row says which one played
-(``other_policy_id``).
+(``other_policy_id``).  A member may be state-reactive (``ShortestPathPolicy``,
+Driving-v1's shortest-path agents): it acts on the true state before the joint
+action and still takes its word of the agent's stream.
 
 With ``belief_tracker=BeliefStatTracker(planner, EpisodeEnvView(...), ...)`` the
 row also carries the tracker's ``belief_*_acc`` columns
@@ -113,6 +115,24 @@ def episode_population(planner, other_agents, known_ids=()):
     ids = [pol.policy_id for pol in other_agents]
     known = list(known_ids or [])
     return ids, probs, [known.index(i) if i in known else -1 for i in ids]
+
+
+def population_kinds(planner, other_agents):
+    """The population's ``pomcp_policy_kinds`` entries, [(kind, param0, param1)]
+    per policy, or ``None`` when every policy is a fixed distribution (or there
+    is no population): what ``engine.episodes_set_population_kinds`` takes after
+    ``episodes_set_population``.  A reactive policy needs the engine's model to
+    be the environment it acts in (``NotImplementedError`` otherwise, before
+    anything is launched)."""
+    from posggym_baselines_amd.planning.policies import is_reactive, policy_kinds
+    if other_agents is None or not any(is_reactive(pol) for pol in other_agents):
+        return None
+    ego = getattr(planner.engine, "ego", None)     # the planning agent's index
+    ego = None if ego is None else planner.engine.model.possible_agents[ego]
+    for pol in other_agents:
+        if is_reactive(pol) and pol.agent_id == ego:
+            raise ValueError(f"{pol.policy_id} is built for agent {ego!r}, the planning agent")
+    return policy_kinds(planner.engine.model, other_agents)
 
 
 def play_batch(planner, what, begin, fetch, slots, max_steps, on_step, entries=None,
@@ -234,7 +254,7 @@ class UniformRandomAgents:
     def reset(self):
         self._ctr = {i: 0 for i in self.model.possible_agents}
 
-    def act(self, agent_id: str) -> int:
+    def act(self, agent_id: str, state=None) -> int:
         from posggym_baselines_amd._native import check, load
         j = self._ctr[agent_id]
         self._ctr[agent_id] = j + 1
@@ -247,25 +267,30 @@ class UniformRandomAgents:
 def check_population(population, num_actions: Optional[int] = None):
     """The population's action distributions (``get_pi`` in action order), after
     the checks both episode loops make: 1 to ``POMCP_MAX_TYPE_POLICIES``
-    ``FixedDistributionPolicy`` entries with distinct ``policy_id``s, one
-    probability per action (``num_actions``; default: the first policy's)."""
+    ``FixedDistributionPolicy`` or state-reactive (``ShortestPathPolicy``)
+    entries with distinct ``policy_id``s, one probability per action
+    (``num_actions``; default: the first policy's).  A reactive policy's row is
+    the uniform distribution: a placeholder nothing draws from."""
     from posggym_baselines_amd._native import POMCP_MAX_TYPE_POLICIES
-    from posggym_baselines_amd.planning.policies import FixedDistributionPolicy
+    from posggym_baselines_amd.planning.policies import FixedDistributionPolicy, is_reactive
     population = list(population)
     if not 1 <= len(population) <= POMCP_MAX_TYPE_POLICIES:
         raise ValueError(f"other_agents needs 1 to {POMCP_MAX_TYPE_POLICIES} policies, "
                          f"not {len(population)}")
     for pol in population:
-        if not isinstance(pol, FixedDistributionPolicy):
+        if not isinstance(pol, FixedDistributionPolicy) and not is_reactive(pol):
             raise NotImplementedError(
                 f"policy {getattr(pol, 'policy_id', pol)!r}: the population holds "
-                "fixed-distribution policies (planning/policies.py)")
+                "fixed-distribution and shortest-path policies (planning/policies.py)")
     ids = [pol.policy_id for pol in population]
     if len(set(ids)) != len(ids):
         raise ValueError(f"other_agents has duplicate policy ids: {ids}")
     probs = []
     for pol in population:
-        pi = pol.get_pi(pol.get_initial_state()).probs
+        if is_reactive(pol):
+            pi = {a: 1.0 / pol.num_actions for a in range(pol.num_actions)}
+        else:
+            pi = pol.get_pi(pol.get_initial_state()).probs
         if num_actions is None:
             num_actions = len(pi)
         if len(pi) != num_actions:
@@ -283,7 +308,10 @@ class PopulationAgents:
     and ``act(i)`` turns word ``j`` of agent ``i``'s policy stream (the counter
     ``UniformRandomAgents`` uses) into an action as CPython's ``random.choices``
     does: ``bisect_right(cumulative(probs), word * 2**-32 * total, 0, n - 1)``
-    (``tm_choice`` of csrc/pomcp_device.h, ``ep_choice`` of csrc/episode_step.h)."""
+    (``tm_choice`` of csrc/pomcp_device.h, ``ep_choice`` of csrc/episode_step.h).
+    A state-reactive member (``ShortestPathPolicy``) acts on ``state``, the true
+    state before the joint action, which ``act`` must then be given; its word of
+    the stream is counted all the same."""
 
     def __init__(self, model, env_seed: int, population):
         from posggym_baselines_amd.envs.driving import ENV_TREE_KEY
@@ -308,10 +336,19 @@ class PopulationAgents:
         self.policy_index = (self._word(S_ENV_POPULATION, 0) * len(self.population)) >> 32
         self.policy_id = self.population[self.policy_index].policy_id
 
-    def act(self, agent_id: str) -> int:
+    def act(self, agent_id: str, state=None) -> int:
         import bisect
+        from posggym_baselines_amd.planning.policies import is_reactive
         j = self._ctr[agent_id]
         self._ctr[agent_id] = j + 1
+        pol = self.population[self.policy_index]
+        if is_reactive(pol):
+            if state is None:
+                raise ValueError(f"{pol.policy_id} acts on the state: act(agent_id, state)")
+            if pol.agent_id != agent_id:
+                raise ValueError(f"{pol.policy_id} is agent {pol.agent_id!r}'s policy, not "
+                                 f"{agent_id!r}'s")
+            return pol.action_from_state(state)
         cum, total = self._tables[self.policy_index]
         x = self._word(S_ENV_POLICY_BASE + int(agent_id), j) * 2.0 ** -32 * total
         return bisect.bisect_right(cum, x, 0, len(cum) - 1)
@@ -327,7 +364,8 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
     ``env_model`` against uniform random other agents; returns the result rows.
 
     ``other_agents``: a population (an ordered list of 1 to 8
-    ``FixedDistributionPolicy`` with distinct ids) for the non-planning agent;
+    ``FixedDistributionPolicy`` or ``ShortestPathPolicy`` with distinct ids) for
+    the non-planning agent;
     every episode draws one of them (``PopulationAgents``), the row gains
     ``other_policy_id`` and a ``belief_tracker``'s env view is told the drawn
     policy's id before the tracker is reset.
@@ -372,7 +410,7 @@ def run_planning_episodes(planner, env_model, num_episodes: int, agent_id: str, 
                        for i in env_model.possible_agents}
             for i in env_model.possible_agents:
                 if i != agent_id:
-                    actions[i] = others.act(i)
+                    actions[i] = others.act(i, state)
             ts = env_model.step(state, actions)
             if on_step is not None:
                 on_step(res["len"], obs, actions, ts)

@@ -50,7 +50,7 @@ from posggym_baselines_amd import _native as N
 from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.engine import EngineBase
 from posggym_baselines_amd.planning.episodes import (episode_guards, episode_population,
-                                                     episode_rows, play_batch)
+                                                     episode_rows, play_batch, population_kinds)
 from posggym_baselines_amd.planning.search_policy import RandomSearchPolicy
 from posggym_baselines_amd.planning.utils import PlanningStatTracker
 
@@ -726,6 +726,9 @@ class BatchedINTMCP:
         if len(seeds) != B:
             raise ValueError(f"env_seeds has {len(seeds)} entries for {B} pairs")
         max_steps = episode_guards(self, "run_episodes", until, max_steps)
+        if population_kinds(self, other_agents) is not None:
+            raise NotImplementedError("I-NTMCP episodes play against fixed-distribution "
+                                      "populations (state-reactive policies: BatchedPOMCP)")
         pop_ids, pop_probs, _ = episode_population(self, other_agents)
         engine = self.engine
 
@@ -779,6 +782,9 @@ class BatchedINTMCP:
             raise ValueError(f"run_episode_queue needs at least {B} env_seeds (one per pair), "
                              f"not {N_}")
         max_steps = episode_guards(self, "run_episode_queue", until, max_steps)
+        if population_kinds(self, other_agents) is not None:
+            raise NotImplementedError("I-NTMCP episodes play against fixed-distribution "
+                                      "populations (state-reactive policies: BatchedPOMCP)")
         pop_ids, pop_probs, _ = episode_population(self, other_agents)
         engine = self.engine
 

@@ -38,7 +38,8 @@ from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.other_policy import (OtherAgentMixturePolicy,
                                                           OtherAgentPolicy,
                                                           RandomOtherAgentPolicy)
-from posggym_baselines_amd.planning.policies import FixedDistributionPolicy
+from posggym_baselines_amd.planning.policies import (FixedDistributionPolicy, is_reactive,
+                                                     policy_kinds)
 from posggym_baselines_amd.planning.pomcp import POMCP
 from posggym_baselines_amd.planning.search_policy import (RandomSearchPolicy, SearchPolicy,
                                                            SearchPolicyWrapper)
@@ -57,12 +58,21 @@ def _is_random_search(policy) -> bool:
     return isinstance(policy, RandomSearchPolicy) or _named(policy, "RandomSearchPolicy")
 
 
-def _fixed_probs(policy, A):
-    """The action distribution of a fixed-distribution policy, action order."""
+def _fixed_probs(policy, A, other=False):
+    """The action distribution of a fixed-distribution policy, action order.
+    ``other``: an other-agent policy, which may be state-reactive; its row is
+    the uniform placeholder nothing draws from (``policy_kinds`` says how it acts)."""
+    if other and is_reactive(policy):
+        return [1.0 / A] * A
+    if is_reactive(policy):
+        raise NotImplementedError(
+            f"policy {policy.policy_id!r}: a state-reactive policy is modelled for the other "
+            "agent only, not as the search, rollout or prior policy")
     if not isinstance(policy, FixedDistributionPolicy):
         raise NotImplementedError(
             f"policy {getattr(policy, 'policy_id', policy)!r}: the engine runs fixed-distribution "
-            "policies (planning/policies.py); recurrent / neural policies are out of scope")
+            "and shortest-path policies (planning/policies.py); recurrent / neural policies are "
+            "out of scope")
     pi = policy.get_pi(policy.get_initial_state()).probs
     if list(pi) != list(range(len(pi))):
         raise NotImplementedError("random.choices over a prior in an order other than the "
@@ -98,18 +108,25 @@ def base_type_tables(model, agent_id, config, other_agent_policies, search_polic
     other = other_agent_policies[others[0]]
     sp = search_policy_probs(model, agent_id, search_policy)
     ego_pi = [1.0 / A] * A if sp is None else sp   # RandomSearchPolicy.get_pi
-    oth, mixture = [], False
+    oth, mixture, kinds = [], False, None
     if _is_random_other(other):
         oth = [[1.0 / A] * A]
     elif isinstance(other, OtherAgentMixturePolicy) or _named(other, "OtherAgentMixturePolicy"):
         mixture = True
-        oth = [_fixed_probs(p, A) for p in other.policies.values()]
+        oth = [_fixed_probs(p, A, other=True) for p in other.policies.values()]
+        kinds = policy_kinds(model, other.policies.values())
         if config.state_belief_only:
             # mcts.py:609-610 passes {} and OtherAgentMixturePolicy.sample_action
             # raises KeyError('policy_id') in the reference
             raise ValueError("an OtherAgentMixturePolicy needs state_belief_only=False (the "
                              "particles carry the other agent's policy)")
     else:
+        if is_reactive(other):
+            # the reference passes such a policy the state {} (mcts.py:609-610):
+            # it has no observation to act on
+            raise NotImplementedError(
+                f"policy {other.policy_id!r}: a state-reactive policy is modelled inside an "
+                "OtherAgentMixturePolicy (state_belief_only=False), whose particles carry it")
         oth = [_fixed_probs(other, A)]
         if not config.state_belief_only:
             # mcts.py:205-210 calls other_agent_policies[j].sample_initial_state(),
@@ -135,6 +152,7 @@ def base_type_tables(model, agent_id, config, other_agent_policies, search_polic
     tp.no_mixture_draw = 0 if mixture else 1
     tp.ego_uniform = 1 if sp is None else 0
     tp.other_uniform = 1 if _is_random_other(other) else 0
+    tp.other_kinds = kinds   # (a Python attribute: PomcpEngine passes it to the engine)
     return tp
 
 

@@ -11,6 +11,11 @@ reference calls on a ``posggym.agents.policy.Policy``: ``policy_id``,
 ``get_initial_state``, ``get_next_state``, ``get_pi(state).probs``,
 ``sample_action``, ``get_value``, ``close``.
 
+``ShortestPathPolicy`` (below) is the one state-reactive kind: Driving-v1's
+heuristic shortest-path agents, which the episode kernels play as members of a
+test population (``other_agents=``) and the type-based search models as members
+of the other agent's mixture.
+
 ``sample_action`` draws like ``random.choices(range(n), weights=probs)``
 (CPython's cumulative-weight bisection) on ``self.rng``; the engine makes the
 same draw on the acting agent's action stream (stream 8 + agent index), one
@@ -77,3 +82,240 @@ def cumulative(weights: Sequence[float]):
         acc = float(w) if acc is None else acc + float(w)
         cum.append(acc)
     return cum, cum[-1] + 0.0
+
+
+# ----------------------------------------------------------------------------
+# State-reactive policies: the Driving-v1 shortest-path agents
+# (csrc/driving_policy.h is the same rule on the packed state words).
+
+_DX = (0, 1, 0, -1)
+_DY = (-1, 0, 1, 0)
+_REVERSE, _STOPPED, _FORWARD_SLOW, _FORWARD_FAST = 0, 1, 2, 3
+_DO_NOTHING, _ACCELERATE, _DECELERATE, _TURN_RIGHT, _TURN_LEFT = 0, 1, 2, 3, 4
+_CELL_VEHICLE, _CELL_WALL, _CELL_EMPTY, _CELL_DEST = 0, 1, 2, 3
+
+# posggym.agents' ids of the reference's Driving population
+# (baseline_exps/env_data/Driving-v1/agents_P0.yaml) -> aggressiveness
+SHORTEST_PATH_POLICY_IDS = {
+    "Driving-v1/A0Shortestpath-v0": 0.0,
+    "Driving-v1/A40Shortestpath-v0": 0.4,
+    "Driving-v1/A60Shortestpath-v0": 0.6,
+    "Driving-v1/A80Shortestpath-v0": 0.8,
+    "Driving-v1/A100Shortestpath-v0": 1.0,
+}
+
+
+class _DrivingGrid:
+    """What the rule reads of a Driving model: the product's ``DrivingModel``
+    (envs/driving.py) or one with the oracle's interface (``model.grid``)."""
+
+    def __init__(self, model):
+        if getattr(model, "env_id", None) != "Driving-v1":
+            raise NotImplementedError(
+                f"shortest-path policies are Driving-v1's, not {getattr(model, 'env_id', model)!r}'s")
+        if len(model.possible_agents) != 2:
+            raise NotImplementedError("shortest-path policies act among two agents")
+        g = getattr(model, "grid", None)
+        if g is not None and hasattr(g, "wall"):
+            self.width, self.height, self.wall, self.dist = g.width, g.height, g.wall, g.dist
+            self.locs, self.init_dir = list(g.locs), list(g.init_dir)
+            self.obs_front, self.obs_back, self.obs_side = \
+                model.obs_front, model.obs_back, model.obs_side
+        else:
+            self.width, self.height = model.width, model.height
+            self.wall, self.dist = model._wall, model._dist
+            self.locs, self.init_dir = list(model.locs), list(model.loc_dirs)
+            self.obs_front, self.obs_back, self.obs_side = model.obs_dim
+
+    def free(self, x, y):
+        return 0 <= x < self.width and 0 <= y < self.height and not self.wall[y][x]
+
+    def observe(self, state, i):
+        """Agent ``i``'s observation tuple of the two vehicles ``state`` (tuples
+        in the field order of the packed word)."""
+        x, y, d = state[i][0], state[i][1], state[i][2]
+        ox, oy = state[1 - i][0], state[1 - i][1]
+        r = (d + 1) & 3
+        dest = self.locs[state[i][4]]
+        cells = []
+        for fwd in range(self.obs_front, -self.obs_back - 1, -1):
+            for side in range(-self.obs_side, self.obs_side + 1):
+                cx = x + fwd * _DX[d] + side * _DX[r]
+                cy = y + fwd * _DY[d] + side * _DY[r]
+                if not self.free(cx, cy):
+                    cells.append(_CELL_WALL)
+                elif (cx, cy) == (ox, oy):
+                    cells.append(_CELL_VEHICLE)
+                elif (cx, cy) == dest:
+                    cells.append(_CELL_DEST)
+                else:
+                    cells.append(_CELL_EMPTY)
+        return (tuple(cells), state[i][3], (x, y), dest, state[i][5], state[i][6])
+
+
+def unpack_vehicle(u: int):
+    """A packed vehicle word (csrc/driving.h) as (x, y, dir, speed, dest,
+    reached, crashed, min_dest_dist, init_dest_dist)."""
+    return (u & 15, (u >> 4) & 15, (u >> 8) & 3, (u >> 10) & 3, (u >> 12) & 7,
+            (u >> 15) & 1, (u >> 16) & 1, (u >> 17) & 127, (u >> 24) & 127)
+
+
+class ShortestPathPolicy:
+    """A Driving-v1 agent that drives the shortest path to its destination and
+    brakes for a vehicle it sees ahead (the build's restatement of
+    ``Driving-v1/A{0,40,60,80,100}Shortestpath-v0``).  ``aggressiveness`` g in [0, 1] becomes two integers,
+
+        caution = ceil((1 - g) * obs_front)   rows ahead in which a vehicle makes it brake
+        vmax    = FORWARD_FAST if g >= 0.5 else FORWARD_SLOW
+
+    the only things the device sees of it (``kind_params``).
+
+    The policy is written the posggym way: its state is the last observation
+    and the heading it tracks through its own turns (``{"obs", "dir"}``), and
+    ``get_pi`` is one-hot on the rule's action.  As an observation is a function
+    of the environment state, ``action_from_state`` picks the same action from
+    the two vehicles alone, which is what the kernels do.  ``sample_action``
+    still draws ``rng.choices`` as ``FixedDistributionPolicy`` does, so the
+    agent's action stream advances one word per action."""
+
+    def __init__(self, model, agent_id: str, policy_id: str, aggressiveness: float, rng=None):
+        import math
+        g = float(aggressiveness)
+        if not 0.0 <= g <= 1.0:
+            raise ValueError(f"{policy_id}: aggressiveness must be in [0, 1], not {aggressiveness}")
+        self.grid = _DrivingGrid(model)
+        self.model = model
+        self.agent_id = agent_id
+        self.policy_id = policy_id
+        self.aggressiveness = g
+        self.caution = int(math.ceil((1.0 - g) * self.grid.obs_front))
+        self.vmax = _FORWARD_FAST if g >= 0.5 else _FORWARD_SLOW
+        self.num_actions = model.action_spaces[agent_id].n
+        self.rng = rng if rng is not None else random.Random()
+
+    @classmethod
+    def from_id(cls, model, agent_id: str, policy_id: str, rng=None):
+        """The policy of one of ``SHORTEST_PATH_POLICY_IDS``."""
+        if policy_id not in SHORTEST_PATH_POLICY_IDS:
+            raise KeyError(f"{policy_id!r} is not one of {sorted(SHORTEST_PATH_POLICY_IDS)}")
+        return cls(model, agent_id, policy_id, SHORTEST_PATH_POLICY_IDS[policy_id], rng)
+
+    def kind_params(self):
+        """(``pomcp_policy_kinds`` kind, param0, param1)."""
+        from posggym_baselines_amd._native import POLICY_DRIVING_SHORTEST_PATH
+        return POLICY_DRIVING_SHORTEST_PATH, self.caution, self.vmax
+
+    # -- the posggym.agents policy interface ---------------------------------
+    def get_initial_state(self):
+        return {"obs": None, "dir": None}
+
+    def get_next_state(self, action, obs, state):
+        if action is None:
+            # the first observation: the agent stands on its start location
+            d = self.grid.init_dir[self.grid.locs.index(tuple(obs[2]))]
+        else:
+            d = state["dir"]
+            prev = state["obs"]
+            if not (prev[4] or prev[5]):      # a finished vehicle no longer turns
+                if action == _TURN_RIGHT:
+                    d = (d + 1) & 3
+                elif action == _TURN_LEFT:
+                    d = (d + 3) & 3
+        return {"obs": obs, "dir": d}
+
+    def action(self, state) -> int:
+        """The rule on the policy state (last observation + tracked heading)."""
+        g = self.grid
+        cells, speed, (x0, y0), dest_xy, reached, crashed = state["obs"]
+        if reached or crashed:
+            return _DO_NOTHING
+        W = 2 * g.obs_side + 1
+        rows = min(self.caution, g.obs_front)
+        if any(cells[(g.obs_front - fwd) * W + c] == _CELL_VEHICLE
+               for fwd in range(1, rows + 1) for c in range(W)):
+            if speed > _STOPPED:
+                return _DECELERATE
+            return _ACCELERATE if speed < _STOPPED else _DO_NOTHING
+        dist = g.dist[g.locs.index(tuple(dest_xy))]
+        best, best_key = 0, None
+        for a in range(5):                     # action order; the first minimum wins
+            d, sp = state["dir"], speed
+            if a == _TURN_RIGHT:
+                d = (d + 1) & 3
+            elif a == _TURN_LEFT:
+                d = (d + 3) & 3
+            elif a == _ACCELERATE:
+                sp = min(sp + 1, _FORWARD_FAST)
+            elif a == _DECELERATE:
+                sp = max(sp - 1, _REVERSE)
+            over = 1 if sp > self.vmax else 0
+            move = d if sp != _REVERSE else (d + 2) & 3
+            x, y, bumped = x0, y0, 0
+            for _ in range(abs(sp - _STOPPED)):   # the model's move, vehicles ignored
+                nx, ny = x + _DX[move], y + _DY[move]
+                if not g.free(nx, ny):
+                    bumped = 1
+                    break
+                x, y = nx, ny
+            here = dist[y][x]
+            fx, fy = x + _DX[d], y + _DY[d]
+            ahead = 0 if here == 0 else (dist[fy][fx] if g.free(fx, fy) else 127)
+            key = (over, bumped, here, ahead)
+            if best_key is None or key < best_key:
+                best, best_key = a, key
+        return best
+
+    def action_from_state(self, state) -> int:
+        """The same action from the environment state: two packed vehicle words
+        (the product model's states) or two vehicle tuples (the oracle's)."""
+        vs = [unpack_vehicle(int(v)) if isinstance(v, int) or hasattr(v, "__index__") else tuple(v)
+              for v in state]
+        i = int(self.agent_id)
+        return self.action({"obs": self.grid.observe(vs, i), "dir": vs[i][2]})
+
+    def get_pi(self, state) -> ActionDistribution:
+        a = self.action(state)
+        return ActionDistribution({k: 1.0 if k == a else 0.0 for k in range(self.num_actions)})
+
+    def sample_action(self, state) -> int:
+        a = self.action(state)
+        weights = [1.0 if k == a else 0.0 for k in range(self.num_actions)]
+        return self.rng.choices(range(self.num_actions), weights=weights, k=1)[0]
+
+    def get_value(self, state) -> float:
+        raise NotImplementedError(f"{self.policy_id} has no value estimates")
+
+    def close(self):
+        pass
+
+
+def is_reactive(policy) -> bool:
+    """Whether ``policy`` acts on the state (``ShortestPathPolicy``) instead of
+    drawing from a fixed distribution."""
+    return isinstance(policy, ShortestPathPolicy)
+
+
+def policy_kinds(model, policies):
+    """``pomcp_policy_kinds`` entries, [(kind, param0, param1)] per policy, or
+    ``None`` when none of them is state-reactive.  A reactive policy must act in
+    ``model``'s environment (``NotImplementedError`` otherwise)."""
+    from posggym_baselines_amd._native import POLICY_FIXED
+    policies = list(policies)
+    if not any(is_reactive(pol) for pol in policies):
+        return None
+    env_id = getattr(model, "env_id", None)
+    for pol in policies:
+        if is_reactive(pol) and pol.model.env_id != env_id:
+            raise NotImplementedError(f"{pol.policy_id} acts in {pol.model.env_id}, not in the "
+                                      f"planner's {env_id}")
+    return [pol.kind_params() if is_reactive(pol) else (POLICY_FIXED, 0, 0) for pol in policies]
+
+
+def mixture_is_reactive(other_agent_policies) -> bool:
+    """Whether any other-agent policy a planner models (alone or in a mixture) is
+    state-reactive."""
+    for pol in other_agent_policies.values():
+        members = getattr(pol, "policies", None)
+        if any(is_reactive(m) for m in (members.values() if members is not None else [pol])):
+            return True
+    return False

@@ -46,8 +46,9 @@ from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.engine import PomcpEngine, search_bytes
 from posggym_baselines_amd.planning.episodes import (belief_acc_columns, check_until,
                                                      episode_guards, episode_population,
-                                                     episode_rows, play_batch)
+                                                     episode_rows, play_batch, population_kinds)
 from posggym_baselines_amd.planning.other_policy import RandomOtherAgentPolicy
+from posggym_baselines_amd.planning.policies import mixture_is_reactive
 from posggym_baselines_amd.planning.search_policy import RandomSearchPolicy, SearchPolicy
 from posggym_baselines_amd.planning.utils import PlanningStatTracker
 
@@ -350,6 +351,8 @@ class POMCP:
             raise ValueError("belief stat 'policy' needs other_policy_ids")
         if "action" in stats and other_actions is None:
             raise ValueError("belief stat 'action' needs other_actions")
+        if "action" in stats and not sbo:
+            refuse_reactive_action_accuracy(self.other_agent_policies)
         q = None
         if "state" in stats:
             q = [int(state[0]), int(state[1])]
@@ -394,6 +397,17 @@ class POMCP:
 
     def __str__(self):
         return "POMCP"
+
+
+def refuse_reactive_action_accuracy(other_agent_policies):
+    """Belief ``action`` accuracy sums a histogram of policies times one action
+    distribution each; a state-reactive policy's action depends on each
+    particle's state, which would need a per-particle evaluation: not built.
+    ``None``: the caller knows the planner models one."""
+    if other_agent_policies is None or mixture_is_reactive(other_agent_policies):
+        raise NotImplementedError(
+            "belief 'action' accuracy with a state-reactive policy among the planner's other-agent "
+            "policies needs a per-particle evaluation (track 'policy' and 'state')")
 
 
 class BatchedPOMCP:
@@ -496,7 +510,9 @@ class BatchedPOMCP:
         after every step (tests: ``episode_states()`` is the debug getter).
 
         ``other_agents``: a population for the other agent, an ordered list of 1
-        to 8 ``FixedDistributionPolicy`` with distinct ids; every tree draws its
+        to 8 ``FixedDistributionPolicy`` or ``ShortestPathPolicy`` (Driving-v1's
+        state-reactive shortest-path agents, ``pomcp_episodes_set_population_kinds``)
+        with distinct ids; every tree draws its
         episode's policy from it as ``PopulationAgents`` does for the serial
         harness, on the device (``pomcp_episodes_set_population``), and the row
         gains ``other_policy_id``.  A policy whose id is one of
@@ -554,11 +570,14 @@ class BatchedPOMCP:
         acc_stats = self._belief_acc_stats(belief_acc)
         if track_per_step and not acc_stats:
             raise ValueError("track_per_step needs belief_acc")
+        kinds = population_kinds(self, other_agents)
         pop_ids, pop_probs, mix = episode_population(self, other_agents, self.other_policy_ids)
         engine = self.engine
 
         def begin(pow_table):
             engine.episodes_set_population(pop_probs, mix)
+            if kinds is not None:
+                engine.episodes_set_population_kinds(kinds)
             engine.episodes_track_belief_acc(bool(acc_stats), track_per_step)
             engine.episodes_begin(seeds, pow_table, max_steps, until, track_states=belief_states,
                                   group=K)
@@ -621,11 +640,14 @@ class BatchedPOMCP:
                              f"not {N}")
         max_steps = episode_guards(self, "run_episode_queue", until)
         acc_stats = self._belief_acc_stats(belief_acc)
+        kinds = population_kinds(self, other_agents)
         pop_ids, pop_probs, mix = episode_population(self, other_agents, self.other_policy_ids)
         engine = self.engine
 
         def begin(pow_table):
             engine.episodes_set_population(pop_probs, mix)
+            if kinds is not None:
+                engine.episodes_set_population_kinds(kinds)
             engine.episodes_track_belief_acc(bool(acc_stats), False)
             engine.episodes_queue_begin(seeds, pow_table, max_steps, until,
                                         track_states=belief_states)
@@ -685,11 +707,14 @@ class BatchedPOMCP:
             raise ValueError(f"run_planner_queue needs at least {G} env_seeds (one per planner of "
                              f"{K} replica trees), not {N}")
         max_steps = episode_guards(self, "run_planner_queue", until)
+        kinds = population_kinds(self, other_agents)
         pop_ids, pop_probs, mix = episode_population(self, other_agents, self.other_policy_ids)
         engine = self.engine
 
         def begin(pow_table):
             engine.episodes_set_population(pop_probs, mix)
+            if kinds is not None:
+                engine.episodes_set_population_kinds(kinds)
             engine.episodes_track_belief_acc(False, False)
             engine.episodes_group_queue_begin(seeds, pow_table, max_steps, until, K)
 
@@ -747,6 +772,8 @@ class BatchedPOMCP:
             raise NotImplementedError(
                 "belief history accuracy: the GPU particles carry no joint history "
                 "(track it only with state_belief_only=True, where it is 0.0)")
+        if "action" in stats and getattr(self.engine, "other_reactive", False):
+            refuse_reactive_action_accuracy(None)
         return stats
 
     def episode_belief_acc(self):

@@ -25,7 +25,8 @@ from typing import Dict, Optional
 from posggym_baselines_amd import _native as N
 from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.other_policy import OtherAgentMixturePolicy
-from posggym_baselines_amd.planning.policies import FixedDistributionPolicy
+from posggym_baselines_amd.planning.policies import (FixedDistributionPolicy, is_reactive,
+                                                     policy_kinds)
 from posggym_baselines_amd.planning.pomcp import POMCP, RootView
 from posggym_baselines_amd.planning.search_policy import SearchPolicy, SearchPolicyWrapper
 
@@ -106,11 +107,17 @@ class POTMMCP(POMCP):
             raise NotImplementedError("POTMMCP searches with a POTMMCPMetaPolicy")
         other = [i for i in model.possible_agents if i != agent_id][0]
         mix = other_agent_policies.get(other)
+        for pol in search_policy.policies.values():
+            if is_reactive(pol):
+                raise NotImplementedError(
+                    f"policy {pol.policy_id!r}: a state-reactive policy is modelled for the other "
+                    "agent only, not as one of the meta-policy's ego policies")
         for pol in list(search_policy.policies.values()) + list(getattr(mix, "policies", {}).values()):
-            if not isinstance(pol, FixedDistributionPolicy):
+            if not isinstance(pol, FixedDistributionPolicy) and not is_reactive(pol):
                 raise NotImplementedError(
                     f"policy {getattr(pol, 'policy_id', pol)!r}: the engine runs fixed-distribution "
-                    "policies (planning/policies.py); recurrent / neural policies are out of scope")
+                    "and shortest-path policies (planning/policies.py); recurrent / neural "
+                    "policies are out of scope")
         if not isinstance(mix, OtherAgentMixturePolicy):
             raise NotImplementedError("POTMMCP's other agent must be an OtherAgentMixturePolicy")
         if config.state_belief_only:
@@ -171,7 +178,9 @@ def type_policy_tables(model, agent_id, meta: "POTMMCPMetaPolicy", mix) -> N.Pom
         for a in range(A):
             tp.ego_pi[k][a] = float(pi.get(a, 0.0))
     for j, oid in enumerate(oth_ids):
-        pi = mix.policies[oid].get_pi({}).probs
+        # (a state-reactive policy's row: the uniform placeholder nothing draws from)
+        pi = {a: 1.0 / A for a in range(A)} if is_reactive(mix.policies[oid]) else \
+            mix.policies[oid].get_pi({}).probs
         for a in range(A):
             tp.other_pi[j][a] = float(pi.get(a, 0.0))
         if oid not in meta.meta_policy:
@@ -184,4 +193,5 @@ def type_policy_tables(model, agent_id, meta: "POTMMCPMetaPolicy", mix) -> N.Pom
     prior = meta.get_expected_action_probs(None, meta.get_initial_state())
     for a in range(A):
         tp.expected_prior[a] = float(prior[a])
+    tp.other_kinds = policy_kinds(model, mix.policies.values())   # (PomcpEngine passes it on)
     return tp

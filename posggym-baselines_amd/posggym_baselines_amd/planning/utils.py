@@ -137,6 +137,9 @@ class BeliefStatTracker:
             raise NotImplementedError(
                 "belief history accuracy: the GPU particles carry no joint history "
                 "(track it only with state_belief_only=True, where it is 0.0)")
+        if "action" in stats_to_track and not planner.config.state_belief_only:
+            from posggym_baselines_amd.planning.pomcp import refuse_reactive_action_accuracy
+            refuse_reactive_action_accuracy(planner.other_agent_policies)
         if any(k in stats_to_track for k in ["policy", "action"]):
             assert all(isinstance(pi, OtherAgentPolicy)
                        for pi in planner.other_agent_policies.values())

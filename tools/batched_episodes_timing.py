@@ -30,6 +30,12 @@ The two routes' ``belief_state_acc`` columns must agree bit for bit.  The record
 is stored under the key ``"belief_acc"`` of the ``--out`` file's record, beside
 the figures already there.
 
+With ``--population`` it times ``run_episodes`` against no population, against
+five fixed distributions and against the five shortest-path agents
+(``planning/policies.py``), one warmed-up run each on a fresh engine: wall time
+per batch step and the device time of the update, the search and the episode
+step kernels.  Stored under the key ``"population"``.
+
 With ``--queue`` it times the episode queue: ``run_episode_queue`` over
 ``--rounds`` x trees seeds (a finished tree refilled on the device) against the
 route there was before, that many successive ``run_episodes`` calls over the
@@ -402,6 +408,44 @@ def belief_acc_timing(fresh, seeds, max_steps):
     return rec, agree
 
 
+def population_timing(fresh, model, seeds):
+    """The --population record: run_episodes against no population, five fixed
+    distributions and the five shortest-path agents (planning/policies.py), one
+    warmed-up run each on a fresh engine: the batch step and the episode step
+    kernels' share of it."""
+    from posggym_baselines_amd.planning.policies import (SHORTEST_PATH_POLICY_IDS,
+                                                         FixedDistributionPolicy,
+                                                         ShortestPathPolicy)
+    weights = [[1 + (a + k) % 5 for a in range(5)] for k in range(5)]
+    pops = {
+        "uniform_agent": None,
+        "fixed_five": [FixedDistributionPolicy(model, "1", f"fixed{k}", w)
+                       for k, w in enumerate(weights)],
+        "shortest_path_five": [ShortestPathPolicy.from_id(model, "1", pid)
+                               for pid in SHORTEST_PATH_POLICY_IDS],
+    }
+    out = {}
+    for name, pop in pops.items():
+        for timed in (False, True):        # (False: the untimed warm-up)
+            bp = fresh()
+            try:
+                t0 = time.perf_counter()
+                rows = bp.run_episodes(seeds, until="all_done", other_agents=pop)
+                sec = time.perf_counter() - t0
+                (upd_ms, search_ms, step_ms), steps = bp.engine.episodes_timing()
+            finally:
+                bp.close()
+        out[name] = {
+            "steps": steps, "episode_steps_total": int(sum(r["len"] for r in rows)),
+            "run_episodes_ms_per_step": sec * 1e3 / steps,
+            "update_ms_per_step": upd_ms / steps, "search_ms_per_step": search_ms / steps,
+            "k_episode_step_ms_per_step": step_ms / steps,
+            "mean_return": sum(r["return"] for r in rows) / len(rows),
+        }
+        print(name, json.dumps(out[name]), flush=True)
+    return out
+
+
 def queue_timing(fresh, seeds, B, until):
     """The --queue comparison: N = len(seeds) episodes through run_episode_queue
     and through N / B successive run_episodes calls on one engine."""
@@ -641,6 +685,9 @@ def main():
     ap.add_argument("--out", default="-", help="JSON record path ('-': stdout only)")
     ap.add_argument("--belief-acc", action="store_true",
                     help="time run_episodes(belief_acc=True) against the on_step route")
+    ap.add_argument("--population", action="store_true",
+                    help="time run_episodes against no population, five fixed distributions and "
+                         "the five shortest-path agents")
     ap.add_argument("--root-parallel", action="store_true",
                     help="time run_episodes(root_parallel=--replicas) against update + search + "
                          "merge_roots + a host step per group (defaults: 64 planners, 64 "
@@ -733,6 +780,20 @@ def main():
                 rec = json.loads(f.read())
         rec["queue" if args.until == "all_done" else "queue_" + args.until] = q_rec
         print(json.dumps(q_rec), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0
+
+    if args.population:
+        pop_rec = dict({"trees": B, "sims": S, "device": torch.cuda.get_device_name(dev)},
+                       **population_timing(fresh, model, seeds))
+        rec = {}
+        if args.out != "-" and os.path.exists(args.out):
+            with open(args.out) as f:
+                rec = json.loads(f.read())
+        rec["population"] = pop_rec
         if args.out != "-":
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
