@@ -42,7 +42,9 @@ typedef enum pomcp_selection {
 
 typedef enum pomcp_env {
   POMCP_ENV_DRIVING = 1,            /* Driving-v1: pomcp_config.grid */
-  POMCP_ENV_PURSUIT_EVASION = 2     /* PursuitEvasion-v1: pomcp_config.pe_grid */
+  POMCP_ENV_PURSUIT_EVASION = 2,    /* PursuitEvasion-v1: pomcp_config.pe_grid */
+  POMCP_ENV_COOPERATIVE_REACHING = 3   /* CooperativeReaching-v0: a pomcp_cr_grid beside the
+                                          config (pomcp_create_env) */
 } pomcp_env;
 
 /* Driving-v1 grid tables (16-wide row stride). */
@@ -64,6 +66,17 @@ typedef struct pomcp_pe_grid {
   int32_t use_progress_reward, pad;
   double reward_norm;             /* R_MAX + R_PROGRESS * longest start-goal path */
 } pomcp_pe_grid;
+
+/* CooperativeReaching-v0 (csrc/cooperative_reaching.h): an S x S grid with a
+ * goal in every corner; coordinates are (x, y). */
+typedef struct pomcp_cr_grid {
+  int32_t size;                   /* S, 3..8 */
+  int32_t obs_distance;           /* Chebyshev distance the other agent is seen at; -1: always */
+  int32_t num_goals;              /* 4 */
+  int32_t pad;
+  uint8_t goal[4][2];             /* one per corner */
+  double goal_value[4];           /* the reward of both agents on goal k */
+} pomcp_cr_grid;
 
 /* MCTSConfig (config.py:8-55) after __post_init__, plus engine sizing. */
 typedef struct pomcp_config {
@@ -145,6 +158,14 @@ int32_t pomcp_abi_version(void);
 /* MCTS.__init__ (mcts.py:29-91): allocate all per-tree device state.
  * `hip_stream` is a hipStream_t (NULL = the library's own stream). */
 int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomcp_ctx** out);
+/* pomcp_create for an environment whose description travels beside the config
+ * (ABI 7, additive; pomcp_config does not grow): POMCP_ENV_COOPERATIVE_REACHING,
+ * env_desc its pomcp_cr_grid and env_desc_bytes that struct's sizeof.
+ * pomcp_create refuses that env_id, and this call every other
+ * (POMCP_E_UNSUPPORTED).  The environment runs the tree-per-lane search only
+ * (pomcp_set_search_kernel(POMCP_SEARCH_WAVE): POMCP_E_UNSUPPORTED). */
+int pomcp_create_env(const pomcp_config* cfg, const void* env_desc, int64_t env_desc_bytes,
+                     int32_t device, void* hip_stream, pomcp_ctx** out);
 void pomcp_destroy(pomcp_ctx* ctx);
 const char* pomcp_last_error(const pomcp_ctx* ctx);
 int pomcp_set_stream(pomcp_ctx* ctx, void* hip_stream);
@@ -402,6 +423,20 @@ int pomcp_pe_step(const pomcp_pe_grid* g, const uint32_t state[2], const int32_t
                   uint64_t obs_keys_out[2]);
 int pomcp_pe_obs(const pomcp_pe_grid* g, const uint32_t state[2], uint64_t obs_keys_out[2]);
 
+/* ---- Host (CPU) CooperativeReaching-v0 model from csrc/cooperative_reaching.h */
+int pomcp_cr_sample_initial_state(const pomcp_cr_grid* g, uint64_t seed, uint32_t tree,
+                                  uint32_t* model_ctr, uint32_t state_out[2]);
+/* One joint step (deterministic: no model draw). */
+int pomcp_cr_step(const pomcp_cr_grid* g, const uint32_t state[2], const int32_t actions[2],
+                  uint32_t next_out[2], double rewards_out[2], int32_t terminated_out[2],
+                  uint64_t obs_keys_out[2]);
+int pomcp_cr_obs(const pomcp_cr_grid* g, const uint32_t state[2], uint64_t obs_keys_out[2]);
+/* model.sample_agent_initial_state(agent, obs) with the model stream at
+ * *model_ctr; POMCP_E_INVALID for an observation outside the model. */
+int pomcp_cr_sample_agent_initial_state(const pomcp_cr_grid* g, int32_t agent, uint64_t obs_key,
+                                        uint64_t seed, uint32_t tree, uint32_t* model_ctr,
+                                        uint32_t state_out[2]);
+
 /* ---- Host RNG streams (csrc/philox.h) -----------------------------------
  * out[k] = word (first + k) of Philox stream `stream` under key (seed, tree):
  * the draws of the episode loop's non-planning agents (the reference's
@@ -522,7 +557,8 @@ int pomcp_episodes_timing(pomcp_ctx* ctx, double ms[3], int32_t* steps);
 
 /* ---- Host twin of the per-tree episode step (csrc/episode_step.h) ----------
  * The code k_episode_reset / k_episode_step run per tree, on the host.
- * grid: a pomcp_grid (env_id POMCP_ENV_DRIVING) or a pomcp_pe_grid. */
+ * grid: a pomcp_grid (env_id POMCP_ENV_DRIVING), a pomcp_pe_grid or a
+ * pomcp_cr_grid (POMCP_ENV_COOPERATIVE_REACHING). */
 int pomcp_host_episode_reset(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
                              pomcp_episode_state* st, uint64_t* obs_key_out);
 int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
@@ -620,10 +656,15 @@ int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_ind
  * Its action is a function of the state before the joint action.  The word of
  * the agent's policy stream is still taken at every step, so every counter
  * advances as with a fixed distribution; the policy's pi row is not read (it
- * must still be a valid distribution). */
+ * must still be a valid distribution).
+ * POMCP_POLICY_CR_GOAL is the CooperativeReaching-v0 heuristic agent
+ * (csrc/cooperative_reaching.h cr_goal_action; the registry ids
+ * CooperativeReaching-v0/H{1..5}-v0): param0 is the rule 0..4 that picks its
+ * target goal from its start cell, param1 must be 0.  (Kind 2 is unassigned.) */
 enum {
   POMCP_POLICY_FIXED = 0,
-  POMCP_POLICY_DRIVING_SHORTEST_PATH = 1
+  POMCP_POLICY_DRIVING_SHORTEST_PATH = 1,
+  POMCP_POLICY_CR_GOAL = 3
 };
 typedef struct pomcp_policy_kinds {
   int32_t kind[POMCP_MAX_TYPE_POLICIES];
@@ -633,7 +674,7 @@ typedef struct pomcp_policy_kinds {
 /* The kinds of the population set last (copied; entries past its num_policies
  * are not read); NULL: all fixed, which is also what every
  * pomcp_episodes_set_population leaves.  POMCP_E_STATE without a population,
- * POMCP_E_UNSUPPORTED for a reactive kind on a context that is not Driving-v1,
+ * POMCP_E_UNSUPPORTED for a reactive kind the context's environment does not have,
  * POMCP_E_INVALID for an unknown kind or a parameter out of range. */
 int pomcp_episodes_set_population_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds);
 /* The kinds of a type-based context's other-agent policies (other_pi's order),
@@ -641,8 +682,8 @@ int pomcp_episodes_set_population_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds
  * whose policy is reactive has the other agent act on the simulated state in
  * the tree levels, the rollouts and the rejection reinvigoration.  The word of
  * the action stream is still taken.  NULL: all fixed.  POMCP_E_STATE before
- * pomcp_set_type_policies, POMCP_E_UNSUPPORTED for a reactive kind on a context
- * that is not Driving-v1, POMCP_E_INVALID for a bad kind or parameter or with
+ * pomcp_set_type_policies, POMCP_E_UNSUPPORTED for a reactive kind the context's
+ * environment does not have, POMCP_E_INVALID for a bad kind or parameter or with
  * other_uniform. */
 int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds);
 
@@ -651,6 +692,10 @@ int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds)
 int pomcp_host_driving_policy_actions(const pomcp_grid* grid, int64_t n, const uint32_t* own,
                                       const uint32_t* other, int32_t caution, int32_t vmax,
                                       int32_t* out);
+/* out[i] = cr_goal_action(grid, own[i], rule) for n packed agent words (the
+ * rule never reads the other agent's word). */
+int pomcp_host_cr_policy_actions(const pomcp_cr_grid* grid, int64_t n, const uint32_t* own,
+                                 int32_t rule, int32_t* out);
 /* pomcp_host_episode_step_pop with the population's kinds (NULL: exactly that
  * call). */
 int pomcp_host_episode_step_pop_kinds(int32_t env_id, const void* grid, int32_t ego,

@@ -3,7 +3,8 @@
 // Every kernel is templated on an Env:
 //   Model                      device tables (staged in LDS)
 //   kStepDraws                 model-stream draws per joint step (Driving's
-//                              execution-order shuffle: 1; PursuitEvasion: 0)
+//                              execution-order shuffle: 1; PursuitEvasion,
+//                              CooperativeReaching: 0)
 //   step(m, ego, s0, s1, a_ego, a_oth, j, &n0, &n1, &r, &done)
 //                              joint step + the ego's reward and
 //                              terminated-or-all-done flag (mcts.py:333-344)
@@ -22,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cooperative_reaching.h"
 #include "driving.h"
 #include "driving_policy.h"
 #include "driving_vec.h"
@@ -122,6 +124,44 @@ struct EnvPursuitEvasion {
   __device__ static bool sample_agent_initial(const Model& m, int ego, uint64_t obs, Draw draw,
                                               uint32_t* s0, uint32_t* s1) {
     return pe_sample_agent_initial(m, ego, obs, draw, s0, s1);
+  }
+};
+
+struct EnvCoopReaching {
+  using Model = CrModel;
+  static constexpr int kStepDraws = 0;
+  static constexpr int kEnvId = POMCP_ENV_COOPERATIVE_REACHING;
+  static constexpr int kA = 5;   // actions per agent
+
+  // (straight-line on the VALU: clamped moves, the goal tests compares on the
+  // packed fields; the only model reads are its size, four goal cells and the
+  // value of the joint goal)
+  __device__ static __forceinline__ void step(const Model& m, int ego, uint32_t s0, uint32_t s1,
+                                              uint32_t a_ego, uint32_t a_oth, uint32_t /*j*/,
+                                              uint32_t* n0, uint32_t* n1, double* r, int* done) {
+    cr_step(m, s0, s1, ego == 0 ? a_ego : a_oth, ego == 0 ? a_oth : a_ego, n0, n1, r);
+    *done = done_of(ego, *n0, *n1);
+  }
+  __device__ static __forceinline__ int done_of(int /*ego*/, uint32_t n0, uint32_t n1) {
+    return cr_done(n0, n1) ? 1 : 0;   // both agents terminate together
+  }
+  __device__ static __forceinline__ uint64_t obs_key(const Model& m, int ego, uint32_t n0,
+                                                     uint32_t n1) {
+    return cr_obs_key(m, ego, n0, n1);
+  }
+  __device__ static __forceinline__ uint32_t policy_action(const Model& m, int agent, uint32_t s0,
+                                                           uint32_t s1, int /*kind*/, int p0,
+                                                           int /*p1*/) {
+    return (uint32_t)cr_goal_action(m, agent == 0 ? s0 : s1, p0);
+  }
+  template <class Draw>
+  __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
+    cr_sample_initial_state(m, draw, s0, s1);
+  }
+  template <class Draw>
+  __device__ static bool sample_agent_initial(const Model& m, int ego, uint64_t obs, Draw draw,
+                                              uint32_t* s0, uint32_t* s1) {
+    return cr_sample_agent_initial(m, ego, obs, draw, s0, s1);
   }
 };
 

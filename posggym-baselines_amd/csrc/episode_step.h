@@ -27,6 +27,7 @@
 #define PB_EPISODE_STEP_H_
 #include <stdint.h>
 
+#include "cooperative_reaching.h"
 #include "driving.h"
 #include "driving_policy.h"
 #include "philox.h"
@@ -94,6 +95,37 @@ struct EpPursuitEvasion {
   PB_HD static int policy_action(const Model&, int, uint32_t, uint32_t, int, int, int) { return 0; }
 };
 
+struct EpCoopReaching {
+  using Model = CrModel;
+  static constexpr uint32_t kA = 5;
+  template <class Draw>
+  PB_HD static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
+    cr_sample_initial_state(m, draw, s0, s1);
+  }
+  // pomcp_cr_step: deterministic, one reward for both, both terminate together
+  PB_HD static void step(const Model& m, Streams& /*env*/, uint32_t s0, uint32_t s1, int a0, int a1,
+                         uint32_t* n0, uint32_t* n1, double r[2], int term[2]) {
+    cr_step(m, s0, s1, (uint32_t)a0, (uint32_t)a1, n0, n1, &r[0]);
+    r[1] = r[0];
+    term[0] = term[1] = cr_done(*n0, *n1) ? 1 : 0;
+  }
+  PB_HD static uint64_t obs_key(const Model& m, int agent, uint32_t n0, uint32_t n1) {
+    return cr_obs_key(m, agent, n0, n1);
+  }
+  PB_HD static bool has_kind(int kind) { return kind == POMCP_POLICY_CR_GOAL; }
+  PB_HD static int policy_action(const Model& m, int agent, uint32_t s0, uint32_t s1, int /*kind*/,
+                                 int p0, int /*p1*/) {
+    return cr_goal_action(m, agent == 0 ? s0 : s1, p0);
+  }
+};
+
+// kind / parameters of one policy of a population or a mixture
+// (pomcp_policy_kinds), whichever environment has the kind: false for an
+// unknown kind or a parameter out of range.
+PB_HD bool policy_kind_ok(int kind, int p0, int p1) {
+  return drv_policy_kind_ok(kind, p0, p1) || cr_policy_kind_ok(kind, p0, p1);
+}
+
 // A population's draw tables: random.choices' cumulative weights
 // (itertools.accumulate) and total = cum[-1] + 0.0 per policy
 // (planning/policies.py cumulative), the doubles Python bisects.
@@ -137,7 +169,7 @@ inline int ep_pop_kinds(const pomcp_policy_kinds* kinds, EpPopTables* t) {
   for (int k = 0; k < POMCP_MAX_TYPE_POLICIES; ++k) t->kind[k] = t->p0[k] = t->p1[k] = 0;
   if (kinds == nullptr) return POMCP_OK;
   for (int k = 0; k < t->n; ++k) {
-    if (!drv_policy_kind_ok(kinds->kind[k], kinds->param0[k], kinds->param1[k]))
+    if (!policy_kind_ok(kinds->kind[k], kinds->param0[k], kinds->param1[k]))
       return POMCP_E_INVALID;
     if (kinds->kind[k] != POMCP_POLICY_FIXED && !E::has_kind(kinds->kind[k]))
       return POMCP_E_UNSUPPORTED;

@@ -1,6 +1,7 @@
 // Host-only entry points of libpomcp_hip.so (include/pomcp.h, pomcp_debug.h):
-// the environment side of the episode loop (Driving-v1 / PursuitEvasion-v1
-// from the same driving.h / pursuit_evasion.h the kernels use), the host RNG
+// the environment side of the episode loop (Driving-v1 / PursuitEvasion-v1 /
+// CooperativeReaching-v0 from the same driving.h / pursuit_evasion.h /
+// cooperative_reaching.h the kernels use), the host RNG
 // words and the host log / exp tables -- the reference's step / obs / RNG
 // contract (mcts.py:181-198, 333, 418; exp_utils.py:481).
 //
@@ -24,6 +25,7 @@
 #include <cstring>
 
 #include "belief_stats.h"
+#include "cooperative_reaching.h"
 #include "driving.h"
 #include "driving_policy.h"
 #include "episode_group.h"
@@ -54,6 +56,27 @@ void make_model(const pomcp_grid* g, DrvModel* m) {
   }
   *m = last;
 }
+
+// f(E{}, model) with the episode environment E of env_id (episode_step.h) and
+// its tables built from `grid`
+template <class F>
+void with_host_env(int32_t env_id, const void* grid, F&& f) {
+  if (env_id == POMCP_ENV_DRIVING) {
+    DrvModel m;
+    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
+    f(EpDriving{}, m);
+  } else if (env_id == POMCP_ENV_PURSUIT_EVASION) {
+    PeModel m;
+    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
+    f(EpPursuitEvasion{}, m);
+  } else {
+    CrModel m;
+    build_cr_model(*reinterpret_cast<const pomcp_cr_grid*>(grid), &m);
+    f(EpCoopReaching{}, m);
+  }
+}
+
+int host_env_actions(int32_t env_id) { return env_id == POMCP_ENV_PURSUIT_EVASION ? 4 : 5; }
 }  // namespace
 
 extern "C" {
@@ -119,6 +142,91 @@ int pomcp_host_driving_policy_actions(const pomcp_grid* g, int64_t n, const uint
     return POMCP_E_INVALID;
   const DrvGrid& gg = *reinterpret_cast<const DrvGrid*>(g);
   for (int64_t i = 0; i < n; ++i) out[i] = drv_sp_action(gg, own[i], other[i], caution, vmax);
+  return POMCP_OK;
+}
+
+// ------------------------------------------------- host CooperativeReaching
+
+int pomcp_cr_sample_initial_state(const pomcp_cr_grid* g, uint64_t seed, uint32_t tree,
+                                  uint32_t* model_ctr, uint32_t state_out[2]) {
+  if (!g || !model_ctr || !state_out || !cr_grid_ok(*g)) return POMCP_E_INVALID;
+  CrModel m;
+  build_cr_model(*g, &m);
+  Streams s;
+  s.seed = seed;
+  s.tree = tree;
+  for (int k = 0; k < 5; ++k) s.ctr[k] = 0;
+  s.ctr[2] = *model_ctr;
+  cr_sample_initial_state(m, [&](uint32_t n) { return s.model(n); }, &state_out[0], &state_out[1]);
+  *model_ctr = s.ctr[2];
+  return POMCP_OK;
+}
+
+int pomcp_cr_sample_agent_initial_state(const pomcp_cr_grid* g, int32_t agent, uint64_t obs_key,
+                                        uint64_t seed, uint32_t tree, uint32_t* model_ctr,
+                                        uint32_t state_out[2]) {
+  if (!g || !model_ctr || !state_out || (agent != 0 && agent != 1) || !cr_grid_ok(*g))
+    return POMCP_E_INVALID;
+  CrModel m;
+  build_cr_model(*g, &m);
+  Streams s;
+  s.seed = seed;
+  s.tree = tree;
+  for (int k = 0; k < 5; ++k) s.ctr[k] = 0;
+  s.ctr[2] = *model_ctr;
+  const bool ok = cr_sample_agent_initial(m, agent, obs_key, [&](uint32_t n) { return s.model(n); },
+                                          &state_out[0], &state_out[1]);
+  *model_ctr = s.ctr[2];
+  return ok ? POMCP_OK : POMCP_E_INVALID;
+}
+
+// false: a word whose cell lies outside the grid
+static bool cr_state_ok(const CrModel& m, const uint32_t state[2]) {
+  for (int i = 0; i < 2; ++i)
+    if ((int)cr_x(state[i]) >= m.size || (int)cr_y(state[i]) >= m.size) return false;
+  return true;
+}
+
+int pomcp_cr_step(const pomcp_cr_grid* g, const uint32_t state[2], const int32_t actions[2],
+                  uint32_t next_out[2], double rewards_out[2], int32_t terminated_out[2],
+                  uint64_t obs_keys_out[2]) {
+  if (!g || !state || !actions || !next_out || !rewards_out || !terminated_out || !obs_keys_out ||
+      !cr_grid_ok(*g))
+    return POMCP_E_INVALID;
+  for (int i = 0; i < 2; ++i)
+    if (actions[i] < 0 || actions[i] > 4) return POMCP_E_INVALID;
+  CrModel m;
+  build_cr_model(*g, &m);
+  if (!cr_state_ok(m, state)) return POMCP_E_INVALID;
+  double r;
+  cr_step(m, state[0], state[1], (uint32_t)actions[0], (uint32_t)actions[1], &next_out[0],
+          &next_out[1], &r);
+  for (int i = 0; i < 2; ++i) {
+    rewards_out[i] = r;
+    terminated_out[i] = cr_done(next_out[0], next_out[1]) ? 1 : 0;
+    obs_keys_out[i] = cr_obs_key(m, i, next_out[0], next_out[1]);
+  }
+  return POMCP_OK;
+}
+
+int pomcp_cr_obs(const pomcp_cr_grid* g, const uint32_t state[2], uint64_t obs_keys_out[2]) {
+  if (!g || !state || !obs_keys_out || !cr_grid_ok(*g)) return POMCP_E_INVALID;
+  CrModel m;
+  build_cr_model(*g, &m);
+  if (!cr_state_ok(m, state)) return POMCP_E_INVALID;
+  for (int i = 0; i < 2; ++i) obs_keys_out[i] = cr_obs_key(m, i, state[0], state[1]);
+  return POMCP_OK;
+}
+
+// The heuristic agents' rule (cooperative_reaching.h), the code the kernels run.
+int pomcp_host_cr_policy_actions(const pomcp_cr_grid* g, int64_t n, const uint32_t* own,
+                                 int32_t rule, int32_t* out) {
+  if (!g || n < 0 || (n > 0 && (!own || !out)) || !cr_grid_ok(*g) ||
+      !cr_policy_kind_ok(POMCP_POLICY_CR_GOAL, rule, 0))
+    return POMCP_E_INVALID;
+  CrModel m;
+  build_cr_model(*g, &m);
+  for (int64_t i = 0; i < n; ++i) out[i] = cr_goal_action(m, own[i], rule);
   return POMCP_OK;
 }
 
@@ -227,23 +335,20 @@ int pomcp_pe_obs(const pomcp_pe_grid* g, const uint32_t state[2], uint64_t obs_k
 // the host, through the same episode_step.h.
 namespace {
 bool episode_env_ok(int32_t env_id, const void* grid, int32_t ego) {
-  return grid != nullptr && (ego == 0 || ego == 1) &&
-         (env_id == POMCP_ENV_DRIVING || env_id == POMCP_ENV_PURSUIT_EVASION);
+  if (grid == nullptr || (ego != 0 && ego != 1)) return false;
+  if (env_id == POMCP_ENV_COOPERATIVE_REACHING)
+    return cr_grid_ok(*reinterpret_cast<const pomcp_cr_grid*>(grid));
+  return env_id == POMCP_ENV_DRIVING || env_id == POMCP_ENV_PURSUIT_EVASION;
 }
+
 }  // namespace
 
 int pomcp_host_episode_reset(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
                              pomcp_episode_state* st, uint64_t* obs_key_out) {
   if (!episode_env_ok(env_id, grid, ego) || !st || !obs_key_out) return POMCP_E_INVALID;
-  if (env_id == POMCP_ENV_DRIVING) {
-    DrvModel m;
-    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
-    *obs_key_out = episode_reset<EpDriving>(m, ego, env_seed, st);
-  } else {
-    PeModel m;
-    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
-    *obs_key_out = episode_reset<EpPursuitEvasion>(m, ego, env_seed, st);
-  }
+  with_host_env(env_id, grid, [&](auto e, const auto& m) {
+    *obs_key_out = episode_reset<decltype(e)>(m, ego, env_seed, st);
+  });
   return POMCP_OK;
 }
 
@@ -254,15 +359,9 @@ int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
   if (!episode_env_ok(env_id, grid, ego) || !in || !pow_table || !st || !out || max_steps < 1 ||
       (until != POMCP_UNTIL_AGENT_DONE && until != POMCP_UNTIL_ALL_DONE))
     return POMCP_E_INVALID;
-  if (env_id == POMCP_ENV_DRIVING) {
-    DrvModel m;
-    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
-    episode_step<EpDriving>(m, ego, *in, pow_table, max_steps, until, st, out);
-  } else {
-    PeModel m;
-    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
-    episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, st, out);
-  }
+  with_host_env(env_id, grid, [&](auto e, const auto& m) {
+    episode_step<decltype(e)>(m, ego, *in, pow_table, max_steps, until, st, out);
+  });
   return POMCP_OK;
 }
 
@@ -278,19 +377,12 @@ int pomcp_host_episode_reset_pop(int32_t env_id, const void* grid, int32_t ego, 
     ps = &local;
   }
   EpPopTables t;
-  if (pop && !ep_pop_tables(*pop, env_id == POMCP_ENV_DRIVING ? (int)EpDriving::kA
-                                                              : (int)EpPursuitEvasion::kA, &t))
+  if (pop && !ep_pop_tables(*pop, host_env_actions(env_id), &t))
     return POMCP_E_INVALID;
   const EpPopTables* tp = pop ? &t : nullptr;
-  if (env_id == POMCP_ENV_DRIVING) {
-    DrvModel m;
-    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
-    *obs_key_out = episode_reset<EpDriving>(m, ego, env_seed, tp, st, ps);
-  } else {
-    PeModel m;
-    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
-    *obs_key_out = episode_reset<EpPursuitEvasion>(m, ego, env_seed, tp, st, ps);
-  }
+  with_host_env(env_id, grid, [&](auto e, const auto& m) {
+    *obs_key_out = episode_reset<decltype(e)>(m, ego, env_seed, tp, st, ps);
+  });
   return POMCP_OK;
 }
 
@@ -307,25 +399,18 @@ int pomcp_host_episode_step_pop_kinds(int32_t env_id, const void* grid, int32_t 
     return POMCP_E_INVALID;
   EpPopTables t;
   if (pop) {
-    if (!ps || !ep_pop_tables(*pop, env_id == POMCP_ENV_DRIVING ? (int)EpDriving::kA
-                                                                : (int)EpPursuitEvasion::kA, &t) ||
+    if (!ps || !ep_pop_tables(*pop, host_env_actions(env_id), &t) ||
         ps->policy_index < 0 || ps->policy_index >= t.n)
       return POMCP_E_INVALID;
-    const int rc = env_id == POMCP_ENV_DRIVING ? ep_pop_kinds<EpDriving>(kinds, &t)
-                                               : ep_pop_kinds<EpPursuitEvasion>(kinds, &t);
+    int rc = POMCP_OK;
+    with_host_env(env_id, grid, [&](auto e, const auto&) { rc = ep_pop_kinds<decltype(e)>(kinds, &t); });
     if (rc != POMCP_OK) return rc;
   }
   const EpPopTables* tp = pop ? &t : nullptr;
   const int k = pop ? ps->policy_index : -1;
-  if (env_id == POMCP_ENV_DRIVING) {
-    DrvModel m;
-    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
-    episode_step<EpDriving>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
-  } else {
-    PeModel m;
-    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
-    episode_step<EpPursuitEvasion>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
-  }
+  with_host_env(env_id, grid, [&](auto e, const auto& m) {
+    episode_step<decltype(e)>(m, ego, *in, pow_table, max_steps, until, tp, k, st, out);
+  });
   return POMCP_OK;
 }
 
@@ -380,25 +465,17 @@ int intmcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,
     return POMCP_E_INVALID;
   EpPopTables t;
   if (pop) {
-    if (!ps || !ep_pop_tables(*pop, env_id == POMCP_ENV_DRIVING ? (int)EpDriving::kA
-                                                                : (int)EpPursuitEvasion::kA, &t) ||
+    if (!ps || !ep_pop_tables(*pop, host_env_actions(env_id), &t) ||
         ps->policy_index < 0 || ps->policy_index >= t.n)
       return POMCP_E_INVALID;
   }
   const EpPopTables* tp = pop ? &t : nullptr;
   const int k = pop ? ps->policy_index : -1;
   int parked = 0;
-  if (env_id == POMCP_ENV_DRIVING) {
-    DrvModel m;
-    make_model(reinterpret_cast<const pomcp_grid*>(grid), &m);
-    *next_action = im_episode_step<EpDriving>(m, ego, root, kept, pow_table, max_steps, until, tp, k,
-                                              st, out, &parked);
-  } else {
-    PeModel m;
-    build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
-    *next_action = im_episode_step<EpPursuitEvasion>(m, ego, root, kept, pow_table, max_steps, until,
-                                                     tp, k, st, out, &parked);
-  }
+  with_host_env(env_id, grid, [&](auto e, const auto& m) {
+    *next_action = im_episode_step<decltype(e)>(m, ego, root, kept, pow_table, max_steps, until, tp,
+                                                k, st, out, &parked);
+  });
   return POMCP_OK;
 }
 

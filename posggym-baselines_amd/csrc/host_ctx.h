@@ -35,6 +35,7 @@ struct __attribute__((visibility("hidden"))) HostCtx {
   std::string err;
   DrvModel host_drv;      // the configured environment's device tables
   PeModel host_pe;
+  CrModel host_cr;
   const void* host_model = nullptr;
   size_t model_bytes = 0;
 
@@ -63,8 +64,14 @@ struct __attribute__((visibility("hidden"))) HostCtx {
     stream = nullptr;
   }
 
-  void set_env_model(const pomcp_config& c) {
-    if (c.env_id == POMCP_ENV_PURSUIT_EVASION) {
+  // (cr: the description a POMCP_ENV_COOPERATIVE_REACHING context is created
+  // with, pomcp_create_env; the other environments' travel in the config)
+  void set_env_model(const pomcp_config& c, const pomcp_cr_grid* cr = nullptr) {
+    if (c.env_id == POMCP_ENV_COOPERATIVE_REACHING) {
+      build_cr_model(*cr, &host_cr);
+      host_model = &host_cr;
+      model_bytes = sizeof(CrModel);
+    } else if (c.env_id == POMCP_ENV_PURSUIT_EVASION) {
       build_pe_model(c.pe_grid, &host_pe);
       host_model = &host_pe;
       model_bytes = sizeof(PeModel);
@@ -146,6 +153,15 @@ using Int = std::integral_constant<int, N>;
 template <class Drv, class Pe, class F>
 static void env_dispatch(int32_t env, F&& f) {
   dispatch<Drv, Pe>(env == POMCP_ENV_PURSUIT_EVASION ? 1 : 0, f);
+}
+// the row of a pomcp_env in a table of kernels: Driving, PursuitEvasion, CooperativeReaching
+static inline int env_row(int32_t env) {
+  return env == POMCP_ENV_COOPERATIVE_REACHING ? 2 : (env == POMCP_ENV_PURSUIT_EVASION ? 1 : 0);
+}
+// the same with f(Cr{}): the layers that run all three environments
+template <class Drv, class Pe, class Cr, class F>
+static void env_dispatch3(int32_t env, F&& f) {
+  dispatch<Drv, Pe, Cr>(env_row(env), f);
 }
 
 }  // namespace pb

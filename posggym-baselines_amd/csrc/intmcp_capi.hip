@@ -136,7 +136,7 @@ int intmcp_create(const intmcp_config* cfg, int32_t device, void* hip_stream, in
   };
   if (c.abi_version != POMCP_ABI_VERSION) return bad(POMCP_E_INVALID, "ABI version mismatch");
   if (c.env_id != POMCP_ENV_DRIVING && c.env_id != POMCP_ENV_PURSUIT_EVASION)
-    return bad(POMCP_E_UNSUPPORTED, "env_id");
+    return bad(POMCP_E_UNSUPPORTED, "env_id");   // (CooperativeReaching-v0 included: lane POMCP only)
   if (c.num_agents != 2) return bad(POMCP_E_UNSUPPORTED, "2 agents");
   if (c.num_actions != (c.env_id == POMCP_ENV_DRIVING ? 5 : 4)) return bad(POMCP_E_INVALID, "num_actions");
   if (c.action_selection != POMCP_SEL_UCB && c.action_selection != POMCP_SEL_UNIFORM)

@@ -119,13 +119,13 @@ constexpr int kStepTreeMaxDepth = 8;
 // f(Env{}) with the context's environment (envs.h)
 template <class F>
 static void with_env(const pomcp_ctx* ctx, F&& f) {
-  env_dispatch<EnvDriving, EnvPursuitEvasion>(ctx->dp.env, f);
+  env_dispatch3<EnvDriving, EnvPursuitEvasion, EnvCoopReaching>(ctx->dp.env, f);
 }
 
 // f(Env{}) with the context's environment as the episode kernels know it (episode_step.h)
 template <class F>
 static void with_episode_env(const pomcp_ctx* ctx, F&& f) {
-  env_dispatch<EpDriving, EpPursuitEvasion>(ctx->dp.env, f);
+  env_dispatch3<EpDriving, EpPursuitEvasion, EpCoopReaching>(ctx->dp.env, f);
 }
 
 // The first tree whose status code(t) is an error, named by its kind.
@@ -166,18 +166,26 @@ int pomcp_set_stream(pomcp_ctx* ctx, void* hip_stream) {
   return POMCP_OK;
 }
 
-static int validate(const pomcp_config* c, std::string* why) {
+// (cr: the description beside the config, pomcp_create_env; null from pomcp_create)
+static int validate(const pomcp_config* c, const pomcp_cr_grid* cr, std::string* why) {
   auto bad = [&](const char* m) {
     *why = m;
     return POMCP_E_INVALID;
   };
   if (c->abi_version != POMCP_ABI_VERSION) return bad("ABI version mismatch");
-  if (c->env_id != POMCP_ENV_DRIVING && c->env_id != POMCP_ENV_PURSUIT_EVASION) {
-    *why = "env_id: Driving-v1 or PursuitEvasion-v1";
+  if (c->env_id == POMCP_ENV_COOPERATIVE_REACHING && cr == nullptr) {
+    *why = "env_id: CooperativeReaching-v0 takes its pomcp_cr_grid through pomcp_create_env";
+    return POMCP_E_UNSUPPORTED;
+  }
+  if (c->env_id != POMCP_ENV_DRIVING && c->env_id != POMCP_ENV_PURSUIT_EVASION &&
+      c->env_id != POMCP_ENV_COOPERATIVE_REACHING) {
+    *why = "env_id: Driving-v1, PursuitEvasion-v1 or CooperativeReaching-v0";
     return POMCP_E_UNSUPPORTED;
   }
   if (c->num_agents != 2) { *why = "the engine's models are 2-agent"; return POMCP_E_UNSUPPORTED; }
-  if (c->num_actions != (c->env_id == POMCP_ENV_DRIVING ? 5 : 4)) return bad("num_actions of the model");
+  if (c->num_actions != (c->env_id == POMCP_ENV_PURSUIT_EVASION ? 4 : 5)) return bad("num_actions of the model");
+  if (c->env_id == POMCP_ENV_COOPERATIVE_REACHING && !cr_grid_ok(*cr))
+    return bad("cr grid: size 3..8, four corner goals, obs_distance -1..7");
   if (c->env_id == POMCP_ENV_PURSUIT_EVASION) {
     const pomcp_pe_grid& g = c->pe_grid;
     if (g.width < 1 || g.width > 16 || g.height < 1 || g.height > 16) return bad("pe grid size");
@@ -226,11 +234,29 @@ static int validate(const pomcp_config* c, std::string* why) {
   return POMCP_OK;
 }
 
+static int create_ctx(const pomcp_config* cfg, const pomcp_cr_grid* cr, int32_t device,
+                      void* hip_stream, pomcp_ctx** out);
+
 int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomcp_ctx** out) {
+  return create_ctx(cfg, nullptr, device, hip_stream, out);
+}
+
+int pomcp_create_env(const pomcp_config* cfg, const void* env_desc, int64_t env_desc_bytes,
+                     int32_t device, void* hip_stream, pomcp_ctx** out) {
+  if (!cfg || !out || !env_desc) return POMCP_E_INVALID;
+  *out = nullptr;
+  // (the other environments' descriptions have their place in the config: pomcp_create)
+  if (cfg->env_id != POMCP_ENV_COOPERATIVE_REACHING) return POMCP_E_UNSUPPORTED;
+  if (env_desc_bytes != (int64_t)sizeof(pomcp_cr_grid)) return POMCP_E_INVALID;
+  return create_ctx(cfg, static_cast<const pomcp_cr_grid*>(env_desc), device, hip_stream, out);
+}
+
+static int create_ctx(const pomcp_config* cfg, const pomcp_cr_grid* cr, int32_t device,
+                      void* hip_stream, pomcp_ctx** out) {
   if (!cfg || !out) return POMCP_E_INVALID;
   *out = nullptr;
   std::string why;
-  int rc = validate(cfg, &why);
+  int rc = validate(cfg, cr, &why);
   if (rc != POMCP_OK) {
     std::fprintf(stderr, "pomcp_create: %s\n", why.c_str());
     return rc;
@@ -242,7 +268,7 @@ int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomc
     return rc;
   }
   const pomcp_config& c = *cfg;
-  ctx->set_env_model(c);
+  ctx->set_env_model(c, cr);
   DevParams& d = ctx->dp;
   d.env = c.env_id;
   d.B = c.num_trees;
@@ -413,9 +439,10 @@ static int ensure_compaction_scratch(pomcp_ctx* ctx) {
   // the persistent grid: as many workgroups as are resident at once
   int per_cu = 0, ncu = 0;
   PB_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                  &per_cu, reinterpret_cast<const void*>(d.env == POMCP_ENV_PURSUIT_EVASION
-                                                             ? &k_log_filter<EnvPursuitEvasion>
-                                                             : &k_log_filter<EnvDriving>),
+                  &per_cu, reinterpret_cast<const void*>(
+                               d.env == POMCP_ENV_COOPERATIVE_REACHING ? &k_log_filter<EnvCoopReaching>
+                               : d.env == POMCP_ENV_PURSUIT_EVASION    ? &k_log_filter<EnvPursuitEvasion>
+                                                                       : &k_log_filter<EnvDriving>),
                   kLfThreads, 0));
   PB_TRY(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
   ctx->lf_grid = (per_cu > 0 ? per_cu : 1) * (ncu > 0 ? ncu : 1);
@@ -511,8 +538,9 @@ int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_key
   return first_update_error(ctx);
 }
 
+// (CooperativeReaching-v0 runs the tree-per-lane kernel only)
 static bool wave_search_fits(const pomcp_ctx* ctx) {
-  return ctx->dp.A <= kMaxA &&
+  return ctx->dp.env != POMCP_ENV_COOPERATIVE_REACHING && ctx->dp.A <= kMaxA &&
          (int64_t)ctx->dp.B * ctx->dp.Np * (int64_t)sizeof(LogRec) <= kWaveSearchMaxScratch;
 }
 
@@ -526,6 +554,9 @@ static int resolve_search_kind(const pomcp_ctx* ctx) {
 
 int pomcp_set_search_kernel(pomcp_ctx* ctx, int32_t kind) {
   if (!ctx || kind < POMCP_SEARCH_AUTO || kind > POMCP_SEARCH_WAVE) return POMCP_E_INVALID;
+  if (kind == POMCP_SEARCH_WAVE && ctx->dp.env == POMCP_ENV_COOPERATIVE_REACHING)
+    return fail(ctx, POMCP_E_UNSUPPORTED, "set_search_kernel: CooperativeReaching-v0 has no "
+                                          "wave-per-tree search");
   if (kind == POMCP_SEARCH_WAVE && !wave_search_fits(ctx))
     return fail(ctx, POMCP_E_UNSUPPORTED, "set_search_kernel: wave search scratch too large");
   if (kind == POMCP_SEARCH_WAVE && ctx->dp.tm)
@@ -620,7 +651,7 @@ static int launch_search(pomcp_ctx* ctx, int32_t num_sims, int final_sel) {
   const int tpb = search_tpb(ctx->dp.B);
   const dim3 grid((unsigned)((ctx->dp.B + tpb - 1) / tpb)), block((unsigned)tpb);
   // kernel per (environment, selection rule, workgroup size); the action count is the model's
-  const int e = ctx->dp.env == POMCP_ENV_PURSUIT_EVASION ? 1 : 0;
+  const int e = env_row(ctx->dp.env);
   const int row = (ctx->dp.tm ? 2 : 0) + (tpb == kTPB ? 0 : 1);
   int sims = (int)num_sims, fsel = final_sel;
   void* args[] = {&ctx->dp, &sims, &fsel};
@@ -794,10 +825,13 @@ int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds)
   TmTables t = ctx->host_tm;
   for (int j = 0; j < kTmMax; ++j) t.oth_kind[j] = t.oth_p0[j] = t.oth_p1[j] = 0;
   for (int j = 0; kinds && j < t.n_other; ++j) {
-    if (!drv_policy_kind_ok(kinds->kind[j], kinds->param0[j], kinds->param1[j]))
-      return fail(ctx, POMCP_E_INVALID, "set_type_policy_kinds: kind 0..1, caution 0..15, vmax 0..3");
+    if (!policy_kind_ok(kinds->kind[j], kinds->param0[j], kinds->param1[j]))
+      return fail(ctx, POMCP_E_INVALID, "set_type_policy_kinds: kind 1 (caution 0..15, vmax 0..3), "
+                                        "kind 3 (rule 0..4, 0) or 0");
     if (kinds->kind[j] == POMCP_POLICY_FIXED) continue;
-    if (ctx->dp.env != POMCP_ENV_DRIVING)
+    bool has = false;
+    with_episode_env(ctx, [&](auto e) { has = decltype(e)::has_kind(kinds->kind[j]); });
+    if (!has)
       return fail(ctx, POMCP_E_UNSUPPORTED, "set_type_policy_kinds: the environment has no such "
                                             "reactive policy kind");
     if (t.other_uniform)
@@ -1341,9 +1375,9 @@ int pomcp_episodes_set_population(pomcp_ctx* ctx, const pomcp_episode_population
 
 int pomcp_episodes_set_population_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds) {
   if (!ctx) return POMCP_E_INVALID;
-  return ctx->dp.env == POMCP_ENV_DRIVING
-             ? ctx->set_population_kinds<EpDriving>(ctx, kinds)
-             : ctx->set_population_kinds<EpPursuitEvasion>(ctx, kinds);
+  int rc = POMCP_E_INVALID;
+  with_episode_env(ctx, [&](auto e) { rc = ctx->template set_population_kinds<decltype(e)>(ctx, kinds); });
+  return rc;
 }
 
 int pomcp_episodes_pop_states(pomcp_ctx* ctx, pomcp_episode_pop_state* out) {
@@ -1546,12 +1580,10 @@ int pomcp_debug_env_step(pomcp_ctx* ctx, const uint32_t* in, int32_t n, uint32_t
   if (e == hipSuccess) e = hipMemcpyAsync(din, in, sizeof(uint32_t) * 5 * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (ctx->dp.env == POMCP_ENV_PURSUIT_EVASION)
-      hipLaunchKernelGGL(k_env_selftest<EnvPursuitEvasion>, grid, block, 0, ctx->stream, ctx->dp.model,
+    with_env(ctx, [&](auto env) {
+      hipLaunchKernelGGL(k_env_selftest<decltype(env)>, grid, block, 0, ctx->stream, ctx->dp.model,
                          ctx->dp.ego, (const uint32_t*)din, (int)n, dout);
-    else
-      hipLaunchKernelGGL(k_env_selftest<EnvDriving>, grid, block, 0, ctx->stream, ctx->dp.model,
-                         ctx->dp.ego, (const uint32_t*)din, (int)n, dout);
+    });
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, sizeof(uint32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);

@@ -1389,12 +1389,16 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   template __global__ void k_search<E, POMCP_SEL_UNIFORM, NA, T, TM>(DevParams, int, int);
 PB_SEARCH_INST(EnvDriving, 5, kTPB, 0)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB, 0)
+PB_SEARCH_INST(EnvCoopReaching, 5, kTPB, 0)
 PB_SEARCH_INST(EnvDriving, 5, kTPBSmall, 0)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall, 0)
+PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall, 0)
 PB_SEARCH_INST(EnvDriving, 5, kTPB, 1)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB, 1)
+PB_SEARCH_INST(EnvCoopReaching, 5, kTPB, 1)
 PB_SEARCH_INST(EnvDriving, 5, kTPBSmall, 1)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall, 1)
+PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall, 1)
 #undef PB_SEARCH_INST
 
 #endif  // PB_SEARCH_TU
@@ -1408,8 +1412,10 @@ PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall, 1)
   template __global__ void k_search<E, POMCP_SEL_UNIFORM, NA, T, 0, PB_SEARCH_DL>(DevParams, int, int);
 PB_SEARCH_INST(EnvDriving, 5, kTPB)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB)
+PB_SEARCH_INST(EnvCoopReaching, 5, kTPB)
 PB_SEARCH_INST(EnvDriving, 5, kTPBSmall)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall)
+PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall)
 #undef PB_SEARCH_INST
 #endif  // PB_SEARCH_DL
 
@@ -1430,8 +1436,11 @@ __attribute__((visibility("hidden"))) const void* PB_DL_CAT(pb_search_kernel_dl,
     k_search<EnvDriving, POMCP_SEL_UNIFORM, 5, T, 0, PB_SEARCH_DL>},       \
    {k_search<EnvPursuitEvasion, POMCP_SEL_PUCB, 4, T, 0, PB_SEARCH_DL>,    \
     k_search<EnvPursuitEvasion, POMCP_SEL_UCB, 4, T, 0, PB_SEARCH_DL>,     \
-    k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, 0, PB_SEARCH_DL>}}
-  static const KFn table[2][2][3] = {PB_SEARCH_ROW(kTPB), PB_SEARCH_ROW(kTPBSmall)};
+    k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, 0, PB_SEARCH_DL>},   \
+   {k_search<EnvCoopReaching, POMCP_SEL_PUCB, 5, T, 0, PB_SEARCH_DL>,      \
+    k_search<EnvCoopReaching, POMCP_SEL_UCB, 5, T, 0, PB_SEARCH_DL>,       \
+    k_search<EnvCoopReaching, POMCP_SEL_UNIFORM, 5, T, 0, PB_SEARCH_DL>}}
+  static const KFn table[2][3][3] = {PB_SEARCH_ROW(kTPB), PB_SEARCH_ROW(kTPBSmall)};
 #undef PB_SEARCH_ROW
   return reinterpret_cast<const void*>(table[small][e][sel]);
 }
@@ -1443,7 +1452,7 @@ const void* pb_search_kernel_dl2(int small, int e, int sel);
 const void* pb_search_kernel_dl3(int small, int e, int sel);
 // The k_search instantiation launched for (row = 2 * TM + small workgroups,
 // environment, selection rule, dl = its compile-time depth limit, 0 for the
-// generic kernel; TM = 0 only): pomcp_capi.hip launch_search.
+// generic kernel; TM = 0 only): pomcp_capi.hip launch_search.  e: host_ctx.h env_row.
 __attribute__((visibility("hidden"))) const void* pb_search_kernel(int row, int e, int sel, int dl) {
   static_assert(pb::kRegPath == 3, "one depth-specialised unit per register-path level");
   if (dl == 1) return pb_search_kernel_dl1(row & 1, e, sel);
@@ -1456,8 +1465,11 @@ __attribute__((visibility("hidden"))) const void* pb_search_kernel(int row, int 
     k_search<EnvDriving, POMCP_SEL_UNIFORM, 5, T, TM>},                                           \
    {k_search<EnvPursuitEvasion, POMCP_SEL_PUCB, 4, T, TM>,                                        \
     k_search<EnvPursuitEvasion, POMCP_SEL_UCB, 4, T, TM>,                                         \
-    k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, TM>}}
-  static const KFn table[4][2][3] = {PB_SEARCH_ROW(kTPB, 0), PB_SEARCH_ROW(kTPBSmall, 0),
+    k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, TM>},                                    \
+   {k_search<EnvCoopReaching, POMCP_SEL_PUCB, 5, T, TM>,                                          \
+    k_search<EnvCoopReaching, POMCP_SEL_UCB, 5, T, TM>,                                           \
+    k_search<EnvCoopReaching, POMCP_SEL_UNIFORM, 5, T, TM>}}
+  static const KFn table[4][3][3] = {PB_SEARCH_ROW(kTPB, 0), PB_SEARCH_ROW(kTPBSmall, 0),
                                      PB_SEARCH_ROW(kTPB, 1), PB_SEARCH_ROW(kTPBSmall, 1)};
 #undef PB_SEARCH_ROW
   return reinterpret_cast<const void*>(table[row][e][sel]);

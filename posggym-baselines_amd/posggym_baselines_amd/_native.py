@@ -34,6 +34,7 @@ SEL_PUCB, SEL_UCB, SEL_UNIFORM = 0, 1, 2
 SEARCH_AUTO, SEARCH_LANE, SEARCH_WAVE = 0, 1, 2   # pomcp_search_kernel
 ENV_DRIVING = 1
 ENV_PURSUIT_EVASION = 2
+ENV_COOPERATIVE_REACHING = 3   # created through pomcp_create_env with a PomcpCrGrid
 
 STATUS_NAMES = {
     POMCP_E_INVALID: "POMCP_E_INVALID",
@@ -79,6 +80,17 @@ class PomcpPeGrid(C.Structure):
         ("use_progress_reward", C.c_int32),
         ("pad", C.c_int32),
         ("reward_norm", C.c_double),
+    ]
+
+
+class PomcpCrGrid(C.Structure):
+    _fields_ = [
+        ("size", C.c_int32),
+        ("obs_distance", C.c_int32),
+        ("num_goals", C.c_int32),
+        ("pad", C.c_int32),
+        ("goal", (C.c_uint8 * 2) * 4),
+        ("goal_value", C.c_double * 4),
     ]
 
 
@@ -262,6 +274,7 @@ class PomcpEpisodePopState(C.Structure):
 
 
 POLICY_FIXED, POLICY_DRIVING_SHORTEST_PATH = 0, 1   # pomcp_policy_kinds.kind
+POLICY_CR_GOAL = 3                                  # (2 is unassigned)
 
 
 class PomcpPolicyKinds(C.Structure):
@@ -342,6 +355,8 @@ _PD = C.POINTER(C.c_double)
 SIGNATURES = [
     ("pomcp_abi_version", C.c_int32, []),
     ("pomcp_create", C.c_int, [C.POINTER(PomcpConfig), C.c_int32, C.c_void_p, C.POINTER(_CTX)]),
+    ("pomcp_create_env", C.c_int,
+     [C.POINTER(PomcpConfig), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(_CTX)]),
     ("pomcp_destroy", None, [_CTX]),
     ("pomcp_last_error", C.c_char_p, [_CTX]),
     ("pomcp_set_stream", C.c_int, [_CTX, C.c_void_p]),
@@ -378,6 +393,14 @@ SIGNATURES = [
      [C.POINTER(PomcpPeGrid), C.c_uint64, C.c_uint32, _PU32, _PU32]),
     ("pomcp_pe_step", C.c_int, [C.POINTER(PomcpPeGrid), _PU32, _P32, _PU32, _PD, _P32, _PU64]),
     ("pomcp_pe_obs", C.c_int, [C.POINTER(PomcpPeGrid), _PU32, _PU64]),
+    ("pomcp_cr_sample_initial_state", C.c_int,
+     [C.POINTER(PomcpCrGrid), C.c_uint64, C.c_uint32, _PU32, _PU32]),
+    ("pomcp_cr_step", C.c_int, [C.POINTER(PomcpCrGrid), _PU32, _P32, _PU32, _PD, _P32, _PU64]),
+    ("pomcp_cr_obs", C.c_int, [C.POINTER(PomcpCrGrid), _PU32, _PU64]),
+    ("pomcp_cr_sample_agent_initial_state", C.c_int,
+     [C.POINTER(PomcpCrGrid), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, _PU32, _PU32]),
+    ("pomcp_host_cr_policy_actions", C.c_int,
+     [C.POINTER(PomcpCrGrid), C.c_int64, _PU32, C.c_int32, _P32]),
     ("pomcp_philox_words", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
                                      _PU32]),
     ("pomcp_host_log_table", C.c_int, [C.c_int64, C.c_int64, _PD]),

@@ -1,11 +1,12 @@
-"""Environment models the GPU engine implements (Driving-v1, PursuitEvasion-v1)
-and the recognition of a posggym-style ``env.model``."""
+"""Environment models the GPU engine implements (Driving-v1, PursuitEvasion-v1,
+CooperativeReaching-v0) and the recognition of a posggym-style ``env.model``."""
 from posggym_baselines_amd.envs.driving import (  # noqa: F401
     GRIDS,
     DrivingModel,
     pack_obs,
     unpack_obs,
 )
+from posggym_baselines_amd.envs.cooperative_reaching import CooperativeReachingModel  # noqa: F401
 from posggym_baselines_amd.envs.pursuit_evasion import PursuitEvasionModel  # noqa: F401
 
 # posggym registrations the engine restates, with the env kwargs each accepts
@@ -16,6 +17,11 @@ _SUPPORTED = {
                                   "obs_dim": (3, 1, 1)}),
     "PursuitEvasion-v1": (PursuitEvasionModel, {"grid": "16x16", "max_obs_distance": 12,
                                                 "use_progress_reward": True}),
+    # (size 3..8; mode "original" and num_goals 4 only: the model's constructor
+    # raises NotImplementedError for anything else)
+    "CooperativeReaching-v0": (CooperativeReachingModel, {"size": 5, "num_goals": 4,
+                                                          "mode": "original",
+                                                          "obs_distance": None}),
 }
 # posggym env kwargs that do not change the generative model
 _IGNORED_KWARGS = {"render_mode", "max_episode_steps"}

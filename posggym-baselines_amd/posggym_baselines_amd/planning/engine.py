@@ -442,7 +442,14 @@ class PomcpEngine(EngineBase):
         self._cfg = c
         dev = config.device if device is None else device
         ctx = C.c_void_p()
-        rc = lib.pomcp_create(C.byref(c), int(dev), stream, C.byref(ctx))
+        # a model whose description does not travel in the config hands it over
+        # beside it (CooperativeReachingModel.engine_env_desc, pomcp_create_env)
+        desc = model.engine_env_desc() if hasattr(model, "engine_env_desc") else None
+        if desc is not None:
+            rc = lib.pomcp_create_env(C.byref(c), C.cast(C.byref(desc), C.c_void_p),
+                                      C.sizeof(desc), int(dev), stream, C.byref(ctx))
+        else:
+            rc = lib.pomcp_create(C.byref(c), int(dev), stream, C.byref(ctx))
         if rc != N.POMCP_OK:
             raise N.PomcpError(rc, "pomcp_create failed (no GPU, bad config or out of memory)")
         self._ctx = ctx

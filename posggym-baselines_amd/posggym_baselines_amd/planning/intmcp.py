@@ -46,6 +46,18 @@ import psutil
 
 from posggym_baselines_amd.envs import engine_model
 
+# environments the lane-per-tree POMCP engine runs and the I-NTMCP kernels do not
+_NO_INTMCP = ("CooperativeReaching-v0",)
+
+
+def _intmcp_model(model):
+    """``engine_model(model)``, refusing the environments I-NTMCP has no kernels for."""
+    m = engine_model(model)
+    if getattr(m, "env_id", None) in _NO_INTMCP:
+        raise NotImplementedError(f"I-NTMCP does not run {m.env_id} on the GPU "
+                                  "(POMCP, IPOMCP, MCTS and POTMMCP do)")
+    return m
+
 from posggym_baselines_amd import _native as N
 from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.engine import EngineBase
@@ -167,7 +179,7 @@ class IntmcpEngine(EngineBase):
                  searches=None, device=None, stream=None, tree_key_base=0, seed=None,
                  wall_clock=False, nesting_level=1):
         lib = N.load()
-        model = engine_model(model)   # posggym-style models by spec.id + kwargs
+        model = _intmcp_model(model)   # posggym-style models by spec.id + kwargs
         if len(model.possible_agents) != 2:
             raise NotImplementedError("the I-NTMCP engine plans for two agents")
         if config.action_selection not in self.SELECTION:
@@ -175,7 +187,7 @@ class IntmcpEngine(EngineBase):
                 "INTMCP pucb_action_selection reads self.action_space, which INTMCP does not "
                 "define (intmcp.py:645); use 'ucb' or 'uniform'")
         self.model = model
-        self._emodel = engine_model(model)
+        self._emodel = _intmcp_model(model)
         self.config = config
         self.num_pairs = self._B = int(num_pairs)
         if not 0 <= int(nesting_level) <= MAX_NESTING:
@@ -481,7 +493,7 @@ class INTMCP:
             lv: {i: search_policy_probs(model, i, pol) for i, pol in pols.items()}
             for lv, pols in (search_policies or {}).items()}
         self.model = model
-        self._emodel = engine_model(model)
+        self._emodel = _intmcp_model(model)
         self.agent_id = agent_id
         self.config = config
         self.nesting_level = nesting_level

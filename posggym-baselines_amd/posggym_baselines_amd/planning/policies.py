@@ -11,10 +11,11 @@ reference calls on a ``posggym.agents.policy.Policy``: ``policy_id``,
 ``get_initial_state``, ``get_next_state``, ``get_pi(state).probs``,
 ``sample_action``, ``get_value``, ``close``.
 
-``ShortestPathPolicy`` (below) is the one state-reactive kind: Driving-v1's
-heuristic shortest-path agents, which the episode kernels play as members of a
-test population (``other_agents=``) and the type-based search models as members
-of the other agent's mixture.
+``ShortestPathPolicy`` and ``GoalHeuristicPolicy`` (below) are the
+state-reactive kinds: Driving-v1's heuristic shortest-path agents and
+CooperativeReaching-v0's goal heuristics H1 .. H5, which the episode kernels
+play as members of a test population (``other_agents=``) and the type-based
+search models as members of the other agent's mixture.
 
 ``sample_action`` draws like ``random.choices(range(n), weights=probs)``
 (CPython's cumulative-weight bisection) on ``self.rng``; the engine makes the
@@ -289,10 +290,136 @@ class ShortestPathPolicy:
         pass
 
 
+# ----------------------------------------------------------------------------
+# The CooperativeReaching-v0 heuristic agents (csrc/cooperative_reaching.h
+# cr_goal_action is the same rule on the packed state word).
+
+# posggym.agents' ids of the reference's CooperativeReaching population
+# (baseline_exps/env_data/CooperativeReaching-v0/agents_P0.yaml) -> rule
+GOAL_HEURISTIC_POLICY_IDS = {
+    "CooperativeReaching-v0/H1-v0": 0,    # closest goal
+    "CooperativeReaching-v0/H2-v0": 1,    # furthest goal
+    "CooperativeReaching-v0/H3-v0": 2,    # closest goal of value 1.0
+    "CooperativeReaching-v0/H4-v0": 3,    # furthest goal of value 1.0
+    "CooperativeReaching-v0/H5-v0": 4,    # closest goal of value 0.75
+}
+_CR_DO_NOTHING, _CR_UP, _CR_DOWN, _CR_LEFT, _CR_RIGHT = 0, 1, 2, 3, 4
+
+
+class GoalHeuristicPolicy:
+    """A CooperativeReaching-v0 agent that walks to one goal, picked from the
+    cell it started on (the build's restatement of
+    ``CooperativeReaching-v0/H{1..5}-v0``).  ``rule`` 0..4 is the
+    only thing the device sees of it (``kind_params``): closest, furthest,
+    closest of value 1.0, furthest of value 1.0, closest of value 0.75, by
+    Manhattan distance with ties to the lower goal index.  It moves
+    horizontally when ``|gx - x| >= |gy - y|`` and ``gx != x``, otherwise
+    vertically, and stays on its target.
+
+    The policy is written the posggym way: its state is the first and the last
+    own position it observed (``{"start", "pos"}``) and ``get_pi`` is one-hot on
+    the rule's action.  The start cell is part of the environment state, so
+    ``action_from_state`` picks the same action from the two state words alone,
+    which is what the kernels do.  ``sample_action`` still draws
+    ``rng.choices`` as ``FixedDistributionPolicy`` does, so the agent's action
+    stream advances one word per action."""
+
+    def __init__(self, model, agent_id: str, policy_id: str, rule: int, rng=None):
+        if getattr(model, "env_id", None) != "CooperativeReaching-v0":
+            raise NotImplementedError(
+                f"goal heuristics are CooperativeReaching-v0's, not "
+                f"{getattr(model, 'env_id', model)!r}'s")
+        if len(model.possible_agents) != 2:
+            raise NotImplementedError("goal heuristics act among two agents")
+        if isinstance(rule, bool) or int(rule) != rule or not 0 <= int(rule) <= 4:
+            raise ValueError(f"{policy_id}: rule must be 0..4, not {rule}")
+        self.model = model
+        self.agent_id = agent_id
+        self.policy_id = policy_id
+        self.rule = int(rule)
+        self.goals = [tuple(g) for g in model.goals]
+        self.goal_values = [float(v) for v in model.goal_values]
+        self.num_actions = model.action_spaces[agent_id].n
+        self.rng = rng if rng is not None else random.Random()
+
+    @classmethod
+    def from_id(cls, model, agent_id: str, policy_id: str, rng=None):
+        """The policy of one of ``GOAL_HEURISTIC_POLICY_IDS``."""
+        if policy_id not in GOAL_HEURISTIC_POLICY_IDS:
+            raise KeyError(f"{policy_id!r} is not one of {sorted(GOAL_HEURISTIC_POLICY_IDS)}")
+        return cls(model, agent_id, policy_id, GOAL_HEURISTIC_POLICY_IDS[policy_id], rng)
+
+    def kind_params(self):
+        """(``pomcp_policy_kinds`` kind, param0, param1)."""
+        from posggym_baselines_amd._native import POLICY_CR_GOAL
+        return POLICY_CR_GOAL, self.rule, 0
+
+    def target(self, start):
+        """The index of the goal the agent heads for from the cell ``start``."""
+        if self.rule in (2, 3):
+            cand = [k for k, v in enumerate(self.goal_values) if v == 1.0]
+        elif self.rule == 4:
+            cand = [k for k, v in enumerate(self.goal_values) if v == 0.75]
+        else:
+            cand = list(range(len(self.goals)))
+        if not cand:
+            return 0
+        dist = lambda k: abs(self.goals[k][0] - start[0]) + abs(self.goals[k][1] - start[1])
+        best = cand[0]
+        for k in cand[1:]:                 # index order; the first extremum wins
+            if (dist(k) > dist(best)) if self.rule in (1, 3) else (dist(k) < dist(best)):
+                best = k
+        return best
+
+    # -- the posggym.agents policy interface ---------------------------------
+    def get_initial_state(self):
+        return {"start": None, "pos": None}
+
+    def get_next_state(self, action, obs, state):
+        pos = (int(obs[0][0]), int(obs[0][1]))
+        return {"start": pos if state["start"] is None else state["start"], "pos": pos}
+
+    def action(self, state) -> int:
+        """The rule on the policy state (first and last own position)."""
+        gx, gy = self.goals[self.target(state["start"])]
+        x, y = state["pos"]
+        dx, dy = gx - x, gy - y
+        if dx == 0 and dy == 0:
+            return _CR_DO_NOTHING
+        if abs(dx) >= abs(dy) and dx != 0:
+            return _CR_LEFT if dx < 0 else _CR_RIGHT
+        return _CR_UP if dy < 0 else _CR_DOWN
+
+    def action_from_state(self, state) -> int:
+        """The same action from the environment state: two packed agent words
+        (the product model's states) or two ``(x, y, start x, start y, ...)``
+        tuples."""
+        v = state[int(self.agent_id)]
+        if isinstance(v, int) or hasattr(v, "__index__"):
+            v = int(v)
+            v = (v & 7, (v >> 3) & 7, (v >> 6) & 7, (v >> 9) & 7)
+        return self.action({"start": (v[2], v[3]), "pos": (v[0], v[1])})
+
+    def get_pi(self, state) -> ActionDistribution:
+        a = self.action(state)
+        return ActionDistribution({k: 1.0 if k == a else 0.0 for k in range(self.num_actions)})
+
+    def sample_action(self, state) -> int:
+        a = self.action(state)
+        weights = [1.0 if k == a else 0.0 for k in range(self.num_actions)]
+        return self.rng.choices(range(self.num_actions), weights=weights, k=1)[0]
+
+    def get_value(self, state) -> float:
+        raise NotImplementedError(f"{self.policy_id} has no value estimates")
+
+    def close(self):
+        pass
+
+
 def is_reactive(policy) -> bool:
-    """Whether ``policy`` acts on the state (``ShortestPathPolicy``) instead of
-    drawing from a fixed distribution."""
-    return isinstance(policy, ShortestPathPolicy)
+    """Whether ``policy`` acts on the state (``ShortestPathPolicy``,
+    ``GoalHeuristicPolicy``) instead of drawing from a fixed distribution."""
+    return isinstance(policy, (ShortestPathPolicy, GoalHeuristicPolicy))
 
 
 def policy_kinds(model, policies):
