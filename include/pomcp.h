@@ -686,6 +686,35 @@ int pomcp_episodes_set_population_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds
  * environment does not have, POMCP_E_INVALID for a bad kind or parameter or with
  * other_uniform. */
 int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds);
+/* The kinds of a type-based context's EGO policies (ego_pi's order), valid after
+ * pomcp_set_type_policies, which resets them to fixed.  A reactive ego policy
+ * acts on the simulated state wherever the search reads an ego policy: the
+ * rollout action (the word of the ego's action stream is still taken), the
+ * prior of a node created under it (one-hot on its action at that node), the
+ * moving average of a node's prior, and the expected prior of a root made by
+ * pomcp_update, sum_k expected_meta[k] * pi_k(root) normalised by its sum.
+ * expected_meta: num_ego doubles, the normalised expected meta-policy in
+ * ego_pi's order (potmmcp.py:391-420 with a uniform prior over the other
+ * agent's policies); read only when some kind is reactive.  The ego_pi row of
+ * a reactive policy and expected_prior are then not read (they must still be
+ * valid).  Only POMCP_POLICY_CR_GOAL on a CooperativeReaching-v0 context is an
+ * ego kind: the policy must be a function of the ego's own state word at every
+ * node.  NULL kinds: all fixed.  POMCP_E_STATE before
+ * pomcp_set_type_policies, POMCP_E_UNSUPPORTED for a reactive kind on another
+ * environment, POMCP_E_INVALID for a bad kind, parameter or weight, or with
+ * ego_uniform.  pomcp_get_root_prior of a root that has no block yet builds
+ * the line from a root particle (POMCP_E_STATE when it has none). */
+int pomcp_set_type_ego_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds,
+                             const double* expected_meta);
+/* Host twin of the prior line k_search writes under reactive ego policies
+ * (csrc/tm_prior.h): out[i][0 .. 5) for prior code `code` (0: the expected
+ * prior, k + 1: ego policy k's) at the ego word own[i] on a CooperativeReaching
+ * grid.  ego_pi: [num_ego][POMCP_MAX_ACTIONS]; expected_prior: 5 doubles, the
+ * code-0 line when no kind is reactive. */
+int pomcp_host_cr_prior_lines(const pomcp_cr_grid* grid, int32_t num_ego, const double* ego_pi,
+                              const double* expected_prior, const pomcp_policy_kinds* kinds,
+                              const double* expected_meta, int32_t code, int64_t n,
+                              const uint32_t* own, double* out);
 
 /* Host twins.  out[i] = drv_sp_action(grid, own[i], other[i], caution, vmax)
  * for n pairs of packed vehicle words. */

@@ -13,6 +13,8 @@
 //   policy_action(m, agent, s0, s1, kind, p0, p1) a state-reactive policy's
 //                              action for `agent` (pomcp_policy_kinds;
 //                              PursuitEvasion has no reactive kinds)
+//   kEgoKinds                  a reactive kind may be an EGO policy of the
+//                              type-based search (pomcp_set_type_ego_kinds)
 //   sample_initial(m, draw, &s0, &s1)             model.sample_initial_state
 //   sample_agent_initial(m, ego, obs, draw, &s0, &s1)
 //                              model.sample_agent_initial_state (false: obs
@@ -36,6 +38,7 @@ struct EnvDriving {
   static constexpr int kStepDraws = 1;
   static constexpr int kEnvId = POMCP_ENV_DRIVING;
   static constexpr int kA = 5;   // actions per agent
+  static constexpr bool kEgoKinds = false;   // (the ego's own word depends on hidden actions)
 
   __device__ static __forceinline__ void step(const Model& m, int ego, uint32_t s0, uint32_t s1,
                                               uint32_t a_ego, uint32_t a_oth, uint32_t j,
@@ -95,6 +98,7 @@ struct EnvPursuitEvasion {
   static constexpr int kStepDraws = 0;
   static constexpr int kEnvId = POMCP_ENV_PURSUIT_EVASION;
   static constexpr int kA = 4;   // actions per agent
+  static constexpr bool kEgoKinds = false;
 
   __device__ static __forceinline__ void step(const Model& m, int ego, uint32_t s0, uint32_t s1,
                                               uint32_t a_ego, uint32_t a_oth, uint32_t /*j*/,
@@ -132,6 +136,7 @@ struct EnvCoopReaching {
   static constexpr int kStepDraws = 0;
   static constexpr int kEnvId = POMCP_ENV_COOPERATIVE_REACHING;
   static constexpr int kA = 5;   // actions per agent
+  static constexpr bool kEgoKinds = true;   // POMCP_POLICY_CR_GOAL as an ego policy (§22)
 
   // (straight-line on the VALU: clamped moves, the goal tests compares on the
   // packed fields; the only model reads are its size, four goal cells and the

@@ -36,6 +36,7 @@
 #include "intmcp_episode.h"
 #include "philox.h"
 #include "pursuit_evasion.h"
+#include "tm_prior.h"
 #include "../../include/pomcp.h"
 #include "../../include/pomcp_debug.h"
 
@@ -227,6 +228,41 @@ int pomcp_host_cr_policy_actions(const pomcp_cr_grid* g, int64_t n, const uint32
   CrModel m;
   build_cr_model(*g, &m);
   for (int64_t i = 0; i < n; ++i) out[i] = cr_goal_action(m, own[i], rule);
+  return POMCP_OK;
+}
+
+// The prior line of a node under reactive ego policies (tm_prior.h), the code
+// k_search runs: out[i][0 .. 5) for the ego word own[i].
+int pomcp_host_cr_prior_lines(const pomcp_cr_grid* g, int32_t num_ego, const double* ego_pi,
+                              const double* expected_prior, const pomcp_policy_kinds* kinds,
+                              const double* expected_meta, int32_t code, int64_t n,
+                              const uint32_t* own, double* out) {
+  constexpr int A = 5;
+  if (!g || !ego_pi || !expected_prior || !kinds || !expected_meta || n < 0 ||
+      (n > 0 && (!own || !out)) || !cr_grid_ok(*g) || num_ego < 1 || num_ego > kTmEgoMax ||
+      code < 0 || code > num_ego)
+    return POMCP_E_INVALID;
+  double prior[kTmEgoMax + 1][kTmEgoMax] = {};
+  TmEgo e{};
+  for (int a = 0; a < A; ++a) prior[0][a] = expected_prior[a];
+  for (int k = 0; k < num_ego; ++k) {
+    for (int a = 0; a < A; ++a) prior[k + 1][a] = ego_pi[k * POMCP_MAX_ACTIONS + a];
+    if (kinds->kind[k] == POMCP_POLICY_FIXED) continue;
+    if (!cr_policy_kind_ok(kinds->kind[k], kinds->param0[k], kinds->param1[k]))
+      return POMCP_E_INVALID;
+    e.any = 1;
+    e.kind[k] = kinds->kind[k];
+    e.p0[k] = kinds->param0[k];
+    e.p1[k] = kinds->param1[k];
+  }
+  for (int k = 0; k < num_ego; ++k) e.w[k] = expected_meta[k];
+  CrModel m;
+  build_cr_model(*g, &m);
+  for (int64_t i = 0; i < n; ++i) {
+    const uint32_t v = own[i];
+    tm_prior_line(prior, e, num_ego, A, code,
+                  [&](int k) { return cr_goal_action(m, v, e.p0[k]); }, out + i * A);
+  }
   return POMCP_OK;
 }
 

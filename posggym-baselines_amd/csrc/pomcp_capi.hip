@@ -59,6 +59,7 @@ struct pomcp_ctx : HostCtx, EpisodeHost {
   int gather_world = 0;
   int search_kind = POMCP_SEARCH_AUTO;
   TmTables host_tm{};                    // type-based contexts (pomcp_set_type_policies)
+  TmEgo host_tme{};                      // their ego policies' kinds (pomcp_set_type_ego_kinds)
   bool tm_set = false;
   // a lane search with deferred cut-off records ran since the last update /
   // reset / restore: the mode and the kernel stay fixed until the re-root
@@ -311,7 +312,7 @@ static int create_ctx(const pomcp_config* cfg, const pomcp_cr_grid* cr, int32_t 
   if (rc == POMCP_OK)
     rc = ctx->alloc_bytes(d.plog, sizeof(uint32_t) * (size_t)((int64_t)search_waves((int)B) * kWave *
                                                               d.Np * (3 + d.tm)));
-  if (d.tm) alloc(d.tmt, 1);
+  if (d.tm && rc == POMCP_OK) rc = ctx->alloc_bytes(d.tmt, sizeof(TmDev));   // tables + ego kinds
   alloc(d.wlog, search_waves((int)B));
   alloc(d.want, B);
   alloc(d.want_info, B);
@@ -758,6 +759,17 @@ int pomcp_get_root_belief(pomcp_ctx* ctx, int32_t tree, uint32_t* out, int32_t c
   return POMCP_OK;
 }
 
+// The context's tables and ego kinds to p.tmt's TmDev, complete on return.
+static int upload_tm(pomcp_ctx* ctx) {
+  TmDev dev;
+  dev.t = ctx->host_tm;
+  dev.e = ctx->host_tme;
+  const int rc = ctx->upload_bytes(ctx->dp.tmt, &dev, sizeof(dev));
+  if (rc != POMCP_OK) return rc;
+  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return POMCP_OK;
+}
+
 int pomcp_set_type_policies(pomcp_ctx* ctx, const pomcp_type_policies* tp) {
   if (!ctx || !tp) return POMCP_E_INVALID;
   if (!ctx->dp.tm) return fail(ctx, POMCP_E_STATE, "set_type_policies: context is not type_based");
@@ -811,9 +823,9 @@ int pomcp_set_type_policies(pomcp_ctx* ctx, const pomcp_type_policies* tp) {
   std::memset(ctx->host_other_pi, 0, sizeof(ctx->host_other_pi));
   for (int j = 0; j < no; ++j)
     for (int a = 0; a < A; ++a) ctx->host_other_pi[j][a] = tp->other_pi[j][a];
-  const int rc = ctx->upload(ctx->dp.tmt, &ctx->host_tm, 1);
+  ctx->host_tme = TmEgo{};   // every ego policy fixed (pomcp_set_type_ego_kinds)
+  const int rc = upload_tm(ctx);
   if (rc != POMCP_OK) return rc;
-  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->tm_set = true;
   return POMCP_OK;
 }
@@ -842,10 +854,48 @@ int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds)
   }
   PB_TRY(ctx, hipSetDevice(ctx->device));
   ctx->host_tm = t;
-  const int rc = ctx->upload(ctx->dp.tmt, &ctx->host_tm, 1);
-  if (rc != POMCP_OK) return rc;
-  PB_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return POMCP_OK;
+  return upload_tm(ctx);
+}
+
+int pomcp_set_type_ego_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds,
+                             const double* expected_meta) {
+  if (!ctx) return POMCP_E_INVALID;
+  if (!ctx->dp.tm || !ctx->tm_set)
+    return fail(ctx, POMCP_E_STATE, "set_type_ego_kinds: pomcp_set_type_policies first");
+  const TmTables& t = ctx->host_tm;
+  TmEgo e{};
+  for (int k = 0; kinds && k < t.n_ego; ++k) {
+    if (!policy_kind_ok(kinds->kind[k], kinds->param0[k], kinds->param1[k]))
+      return fail(ctx, POMCP_E_INVALID, "set_type_ego_kinds: kind 3 (rule 0..4, 0) or 0");
+    if (kinds->kind[k] == POMCP_POLICY_FIXED) continue;
+    // an ego kind needs the state form of the policy to hold at every node
+    // (DESIGN.md §22): CooperativeReaching's goal heuristics only
+    if (ctx->dp.env != POMCP_ENV_COOPERATIVE_REACHING || kinds->kind[k] != POMCP_POLICY_CR_GOAL)
+      return fail(ctx, POMCP_E_UNSUPPORTED, "set_type_ego_kinds: the environment has no such "
+                                            "reactive ego policy kind");
+    if (t.ego_uniform)
+      return fail(ctx, POMCP_E_INVALID, "set_type_ego_kinds: ego_uniform draws no policy");
+    e.any = 1;
+    e.kind[k] = kinds->kind[k];
+    e.p0[k] = kinds->param0[k];
+    e.p1[k] = kinds->param1[k];
+  }
+  if (e.any) {
+    if (!expected_meta)
+      return fail(ctx, POMCP_E_INVALID, "set_type_ego_kinds: expected_meta is NULL");
+    double sum = 0.0;
+    for (int k = 0; k < t.n_ego; ++k) {
+      if (!(expected_meta[k] >= 0.0) || !(expected_meta[k] <= 1.0 + 1e-9))
+        return fail(ctx, POMCP_E_INVALID, "set_type_ego_kinds: expected_meta in [0, 1]");
+      e.w[k] = expected_meta[k];
+      sum += expected_meta[k];
+    }
+    if (!(sum > 0.0))
+      return fail(ctx, POMCP_E_INVALID, "set_type_ego_kinds: expected_meta sums to 0");
+  }
+  PB_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_tme = e;
+  return upload_tm(ctx);
 }
 
 int pomcp_get_root_prior(pomcp_ctx* ctx, int32_t tree, double* out) {
@@ -856,7 +906,22 @@ int pomcp_get_root_prior(pomcp_ctx* ctx, int32_t tree, double* out) {
   if (rc != POMCP_OK) return rc;
   const int A = ctx->dp.A;
   if (h.root_blk < 0) {   // no block yet: the prior its code names
-    const int code = h.root_code >= 0 && h.root_code <= kTmMax ? h.root_code : 0;
+    const int code = h.root_code >= 0 && h.root_code <= ctx->host_tm.n_ego ? h.root_code : 0;
+    if (ctx->host_tme.any) {
+      // a reactive ego policy's line is a function of the root: built from a
+      // root particle's ego word as the search will build it (never the
+      // placeholder row)
+      if (h.belief_size <= 0)
+        return fail(ctx, POMCP_E_STATE, "get_root_prior: the root has no particle yet");
+      uint4 bp;
+      if ((rc = read_root_belief(ctx, tree, h, 1, &bp)) != POMCP_OK) return rc;
+      const CrModel& m = *static_cast<const CrModel*>(ctx->host_model);
+      const TmEgo& e = ctx->host_tme;
+      const uint32_t own = ctx->dp.ego == 0 ? bp.y : bp.z;
+      tm_prior_line(ctx->host_tm.prior, e, ctx->host_tm.n_ego, A, code,
+                    [&](int k) { return cr_goal_action(m, own, e.p0[k]); }, out);
+      return POMCP_OK;
+    }
     for (int a = 0; a < A; ++a) out[a] = ctx->host_tm.prior[code][a];
     return POMCP_OK;
   }

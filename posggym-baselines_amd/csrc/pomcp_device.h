@@ -15,6 +15,7 @@
 
 #include "driving.h"
 #include "philox.h"
+#include "tm_prior.h"
 #include "../../include/pomcp.h"
 
 namespace pb {
@@ -173,6 +174,15 @@ struct TmTables {
   // Env::policy_action(kind, p0, p1) on the running state; the word is taken
   // either way
   int32_t oth_kind[kTmMax], oth_p0[kTmMax], oth_p1[kTmMax];
+};
+static_assert(kTmMax == kTmEgoMax, "tm_prior.h indexes TmTables::prior rows");
+// What p.tmt points at: the tables every TM kernel stages, then the ego
+// policies' kinds (tm_prior.h), which only an environment with ego kinds
+// (Env::kEgoKinds) reads -- a kernel of another environment is the code it was
+// without them, and Driving's LDS budget is untouched.
+struct TmDev {
+  TmTables t;
+  TmEgo e;
 };
 // random.choices(population, weights): bisect_right(cum, x, 0, n - 1) for
 // x = random() * total, as CPython computes it (a linear scan: n <= 8).

@@ -163,14 +163,22 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   // per-wave LDS counter wcnt (below)
   const WaveLog wl(p.plog, p.Np, wave, TM);
   // TM: the policy tables staged in LDS (every draw and prior reads them)
-  __shared__ __attribute__((aligned(16))) char tm_lds[TM != 0 ? sizeof(TmTables) : 16];
+  // kEgoR: the environment has reactive EGO policy kinds (envs.h kEgoKinds):
+  // their kinds and the expected meta weights (tm_prior.h TmEgo) follow the
+  // tables in p.tmt's TmDev and are staged with them; another environment's
+  // kernel stages and reads the tables alone, as it did without them
+  constexpr bool kEgoR = TM != 0 && Env::kEgoKinds;
+  constexpr size_t kTmBytes = kEgoR ? sizeof(TmDev) : sizeof(TmTables);
+  __shared__ __attribute__((aligned(16))) char tm_lds[TM != 0 ? kTmBytes : 16];
   if constexpr (TM != 0) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(p.tmt);
     uint32_t* dst = reinterpret_cast<uint32_t*>(tm_lds);
-    for (int i = (int)threadIdx.x; i < (int)(sizeof(TmTables) / 4); i += TPB) dst[i] = src[i];
+    for (int i = (int)threadIdx.x; i < (int)(kTmBytes / 4); i += TPB) dst[i] = src[i];
     __syncthreads();
   }
   const TmTables* const tmt = reinterpret_cast<const TmTables*>(tm_lds);
+  // (kEgoR only; a kernel without it never reads through this)
+  const TmEgo* const tme = &reinterpret_cast<const TmDev*>(tm_lds)->e;
   uint32_t pid = 0;   // TM: the running simulation's other-agent policy (its particle's)
   int epol = 0;       // TM: the ego policy drawn for it
   const int islots = p.islots;   // kSlots (fewer: overflow-map tests)
@@ -395,8 +403,11 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     }
   };
   // ObsNode.add_child for every action (mcts.py:279-281, 318-321): zeroed block
-  // (TM: its prior line = the action_probs of prior code `code`)
-  auto alloc_block = [&](int code) -> int {
+  // (TM: its prior line = the action_probs of prior code `code`; (v0, v1): the
+  // node's state, which a reactive ego policy's prior is a function of -- every
+  // simulation that reaches a node carries the ego word its history implies,
+  // DESIGN.md §22)
+  auto alloc_block = [&](int code, uint32_t v0, uint32_t v1) -> int {
     if (PB_ARENA_FULL()) {
       err = POMCP_E_ARENA;
       return -1;
@@ -409,7 +420,20 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     for (int q = 0; q < blk_parts(A + 1); ++q) d[q] = make_uint4(0, 0, 0, 0);
     if constexpr (TM != 0) {
       double* const pr = reinterpret_cast<double*>(d + part_prior(A));
-      for (int q = 0; q < A; ++q) pr[q] = tmt->prior[code][q];
+      if constexpr (kEgoR) {
+        if (tme->any) {   // (divergent per lane, no barrier)
+          double line[kTmMax];
+          tm_prior_line(tmt->prior, *tme, tmt->n_ego, A, code, [&](int kk) {
+            return Env::policy_action(sm, p.ego, v0, v1, tme->kind[kk], tme->p0[kk], tme->p1[kk]);
+          }, line);
+#pragma unroll
+          for (int q = 0; q < A; ++q) pr[q] = line[q];
+        } else {
+          for (int q = 0; q < A; ++q) pr[q] = tmt->prior[code][q];
+        }
+      } else {
+        for (int q = 0; q < A; ++q) pr[q] = tmt->prior[code][q];
+      }
     }
     return b;
   };
@@ -678,7 +702,17 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
     phase = TP_DONE;
   }
   if (phase != TP_DONE) {
-    if (root_blk < 0) root_blk = alloc_block(h->root_code);   // mcts.py:279-281
+    // (a reactive ego policy's prior of the root: by a root particle's state --
+    // every particle of a root carries the same, true, ego word)
+    uint32_t rv0 = 0u, rv1 = 0u;
+    if constexpr (kEgoR) {
+      if (root_blk < 0 && bsize > 0 && tme->any) {
+        const uint4 bp = rbel[0];
+        rv0 = bp.y;
+        rv1 = bp.z;
+      }
+    }
+    if (root_blk < 0) root_blk = alloc_block(h->root_code, rv0, rv1);   // mcts.py:279-281
     if (root_blk < 0 || bsize <= 0) {
       if (err == 0) err = POMCP_E_STATE;
       phase = TP_DONE;
@@ -826,7 +860,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
       ret = 0.0;
       phase = TP_BACKUP;
     } else if (blk < 0) {                               // mcts.py:318-328
-      const int b = alloc_block(code);
+      const int b = alloc_block(code, s0, s1);
       if (b < 0) {
         phase = TP_DONE;
       } else {
@@ -853,7 +887,19 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
   };
   // TM: action_probs of a node += (the drawn policy's pi - them) / its visits
   // (potmmcp.py:259-264), on an arrival at an existing child
+  // (a reactive ego policy's pi: at the node's state (s0, s1), the one before
+  // the step -- both callers run before descend() moves on)
   auto prior_ema = [&](double (&ap)[kMaxA], int nv) {
+    if constexpr (kEgoR) {
+      if (tme->kind[epol] != POMCP_POLICY_FIXED) {
+        const int ak = (int)Env::policy_action(sm, p.ego, s0, s1, tme->kind[epol], tme->p0[epol],
+                                               tme->p1[epol]);
+#pragma unroll
+        for (int q = 0; q < kMaxA; ++q)
+          if (q < A) ap[q] = ap[q] + ((q == ak ? 1.0 : 0.0) - ap[q]) / (double)nv;
+        return;
+      }
+    }
 #pragma unroll
     for (int q = 0; q < kMaxA; ++q)
       if (q < A) ap[q] = ap[q] + (tmt->prior[epol + 1][q] - ap[q]) / (double)nv;
@@ -1084,7 +1130,12 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
         // TM, the simulation's drawn policy (potmmcp.py:221-229)
         const uint32_t aw = d_act_word(p.ego);
         uint32_t ae;
-        if constexpr (TM != 0)
+        if constexpr (kEgoR) {   // a reactive ego policy acts on the state; the word is taken
+          if (tmt->ego_uniform) ae = uniform_int(aw, (uint32_t)A);
+          else if (tme->kind[epol] != POMCP_POLICY_FIXED)
+            ae = Env::policy_action(sm, p.ego, s0, s1, tme->kind[epol], tme->p0[epol], tme->p1[epol]);
+          else ae = (uint32_t)tm_choice(tmt->ego_cum[epol], tmt->ego_tot[epol], A, aw);
+        } else if constexpr (TM != 0)
           ae = tmt->ego_uniform ? uniform_int(aw, (uint32_t)A)
                                 : (uint32_t)tm_choice(tmt->ego_cum[epol], tmt->ego_tot[epol], A, aw);
         else ae = uniform_int(aw, (uint32_t)A);

@@ -435,6 +435,10 @@ SIGNATURES = [
      [C.POINTER(PomcpBeliefCounts), C.c_int32, C.c_int32, _PD, C.c_int32, _PD]),
     ("pomcp_episodes_set_population_kinds", C.c_int, [_CTX, C.POINTER(PomcpPolicyKinds)]),
     ("pomcp_set_type_policy_kinds", C.c_int, [_CTX, C.POINTER(PomcpPolicyKinds)]),
+    ("pomcp_set_type_ego_kinds", C.c_int, [_CTX, C.POINTER(PomcpPolicyKinds), _PD]),
+    ("pomcp_host_cr_prior_lines", C.c_int,
+     [C.POINTER(PomcpCrGrid), C.c_int32, _PD, _PD, C.POINTER(PomcpPolicyKinds), _PD, C.c_int32,
+      C.c_int64, _PU32, _PD]),
     ("pomcp_host_driving_policy_actions", C.c_int,
      [C.POINTER(PomcpGrid), C.c_int64, _PU32, _PU32, C.c_int32, C.c_int32, _P32]),
     ("pomcp_host_episode_step_pop_kinds", C.c_int,

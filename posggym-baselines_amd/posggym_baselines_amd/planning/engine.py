@@ -467,6 +467,17 @@ class PomcpEngine(EngineBase):
             for k, (kind, p0, p1) in enumerate(kinds):
                 rec.kind[k], rec.param0[k], rec.param1[k] = int(kind), int(p0), int(p1)
             self._check(lib.pomcp_set_type_policy_kinds(ctx, C.byref(rec)), "set_type_policy_kinds")
+        # the ego policies' kinds and the expected meta weights (reactive ego
+        # policies); a fixed-only set makes no call
+        ego_kinds = getattr(type_policies, "ego_kinds", None)
+        self.ego_reactive = bool(ego_kinds)
+        if ego_kinds:
+            rec = N.PomcpPolicyKinds()
+            for k, (kind, p0, p1) in enumerate(ego_kinds):
+                rec.kind[k], rec.param0[k], rec.param1[k] = int(kind), int(p0), int(p1)
+            w = (C.c_double * N.POMCP_MAX_TYPE_POLICIES)(*[float(x) for x in
+                                                          type_policies.ego_meta_weights])
+            self._check(lib.pomcp_set_type_ego_kinds(ctx, C.byref(rec), w), "set_type_ego_kinds")
         # search kernel override (tests / benchmarks): POMCP_SEARCH_KERNEL=lane|wave.
         # A type-based (POTMMCP) context has only the lane kernel: the process-wide
         # override does not apply to it (an explicit set_search_kernel still raises)

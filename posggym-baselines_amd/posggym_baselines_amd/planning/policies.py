@@ -15,7 +15,9 @@ reference calls on a ``posggym.agents.policy.Policy``: ``policy_id``,
 state-reactive kinds: Driving-v1's heuristic shortest-path agents and
 CooperativeReaching-v0's goal heuristics H1 .. H5, which the episode kernels
 play as members of a test population (``other_agents=``) and the type-based
-search models as members of the other agent's mixture.
+search models as members of the other agent's mixture.  The goal heuristics
+can be the EGO's policies too -- a meta-policy's members, or a base planner's
+search policy (``ego_policy_kinds``).
 
 ``sample_action`` draws like ``random.choices(range(n), weights=probs)``
 (CPython's cumulative-weight bisection) on ``self.rng``; the engine makes the
@@ -435,6 +437,38 @@ def policy_kinds(model, policies):
         if is_reactive(pol) and pol.model.env_id != env_id:
             raise NotImplementedError(f"{pol.policy_id} acts in {pol.model.env_id}, not in the "
                                       f"planner's {env_id}")
+    return [pol.kind_params() if is_reactive(pol) else (POLICY_FIXED, 0, 0) for pol in policies]
+
+
+def ego_policy_kinds(model, agent_id, policies, role):
+    """``pomcp_policy_kinds`` entries of the EGO's policies (a meta-policy's
+    members, or the one search policy), or ``None`` when all of them draw from a
+    fixed distribution.  A ``GoalHeuristicPolicy`` built for ``agent_id`` on
+    ``model``'s CooperativeReaching-v0 is the one reactive ego policy: its
+    policy state -- the first and the last own position -- is a function of
+    the ego's own state word at every node of the search.
+    Driving's ``ShortestPathPolicy`` is not (a collision moves the ego by the
+    other vehicle's hidden action, and the rule needs a heading the observation
+    does not carry): ``NotImplementedError``, naming ``role``."""
+    from posggym_baselines_amd._native import POLICY_FIXED
+    policies = list(policies)
+    if not any(is_reactive(pol) for pol in policies):
+        return None
+    env_id = getattr(model, "env_id", None)
+    for pol in policies:
+        if not is_reactive(pol):
+            continue
+        if not isinstance(pol, GoalHeuristicPolicy):
+            raise NotImplementedError(
+                f"policy {pol.policy_id!r}: a state-reactive policy is modelled for the other "
+                f"agent only, not as {role}")
+        if pol.model.env_id != env_id:
+            raise NotImplementedError(f"{pol.policy_id} acts in {pol.model.env_id}, not in the "
+                                      f"planner's {env_id}")
+        if pol.agent_id != agent_id:
+            raise NotImplementedError(
+                f"policy {pol.policy_id!r} was built for agent {pol.agent_id!r}, not for the "
+                f"planning agent {agent_id!r}: an ego policy acts on the ego's own state word")
     return [pol.kind_params() if is_reactive(pol) else (POLICY_FIXED, 0, 0) for pol in policies]
 
 

@@ -73,7 +73,9 @@ class POMCP:
     uniform random one (``RandomSearchPolicy``, the reference's POMCP test
     setup, ``tests/planning/test_pomcp.py:36-74``: the plain kernel) or a
     fixed-distribution one (``SearchPolicyWrapper(FixedDistributionPolicy)``:
-    node priors and rollouts, planning/ipomcp.py); history-dependent
+    node priors and rollouts, planning/ipomcp.py) or, on CooperativeReaching-v0,
+    a goal heuristic (``SearchPolicyWrapper(GoalHeuristicPolicy)``, the
+    reference's ``test_pomcp.py:77-117`` pattern); history-dependent
     (network) search policies raise ``NotImplementedError``.
     """
 

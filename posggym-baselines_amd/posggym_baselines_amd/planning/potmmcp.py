@@ -25,8 +25,8 @@ from typing import Dict, Optional
 from posggym_baselines_amd import _native as N
 from posggym_baselines_amd.planning.config import MCTSConfig
 from posggym_baselines_amd.planning.other_policy import OtherAgentMixturePolicy
-from posggym_baselines_amd.planning.policies import (FixedDistributionPolicy, is_reactive,
-                                                     policy_kinds)
+from posggym_baselines_amd.planning.policies import (FixedDistributionPolicy, ego_policy_kinds,
+                                                     is_reactive, policy_kinds)
 from posggym_baselines_amd.planning.pomcp import POMCP, RootView
 from posggym_baselines_amd.planning.search_policy import SearchPolicy, SearchPolicyWrapper
 
@@ -95,7 +95,9 @@ class POTMMCP(POMCP):
     """``potmmcp.py:18-301`` on the GPU: ``POTMMCP(model, agent_id, config,
     other_agent_policies, search_policy)`` with ``other_agent_policies`` =
     {other agent: ``OtherAgentMixturePolicy``} and ``search_policy`` a
-    ``POTMMCPMetaPolicy``, every policy of both a ``FixedDistributionPolicy``.
+    ``POTMMCPMetaPolicy``, every policy of both a ``FixedDistributionPolicy`` or
+    a state-reactive one (``planning/policies.py``; as an ego policy
+    CooperativeReaching's ``GoalHeuristicPolicy`` only).
     Bit-exact with the reference planner (tests/golden/potmmcp_*.json).
     ``root.action_probs`` is the root's prior after the last search."""
 
@@ -107,11 +109,6 @@ class POTMMCP(POMCP):
             raise NotImplementedError("POTMMCP searches with a POTMMCPMetaPolicy")
         other = [i for i in model.possible_agents if i != agent_id][0]
         mix = other_agent_policies.get(other)
-        for pol in search_policy.policies.values():
-            if is_reactive(pol):
-                raise NotImplementedError(
-                    f"policy {pol.policy_id!r}: a state-reactive policy is modelled for the other "
-                    "agent only, not as one of the meta-policy's ego policies")
         for pol in list(search_policy.policies.values()) + list(getattr(mix, "policies", {}).values()):
             if not isinstance(pol, FixedDistributionPolicy) and not is_reactive(pol):
                 raise NotImplementedError(
@@ -163,18 +160,43 @@ class RootViewTM(RootView):
     action_probs: dict = dataclasses.field(default_factory=dict)
 
 
+def expected_meta_weights(meta: "POTMMCPMetaPolicy"):
+    """The normalised expected meta-policy under a uniform prior over the other
+    agent's policies, in ``meta.policies``' order: the first half of
+    ``get_expected_action_probs(None, .)`` (``potmmcp.py:391-420``), the
+    reference's own expressions in its own dict orders.  It does not depend on
+    the node; the engine multiplies it into the ego policies' ``pi`` there."""
+    dist = {k: 1.0 / len(meta.meta_policy) for k in meta.meta_policy}
+    expected = {k: 0.0 for k in meta.policies}
+    for oid, prob in dist.items():
+        for pid, mp in meta.meta_policy[oid].items():
+            expected[pid] += prob * mp
+    total = sum(expected.values())
+    for k in expected:
+        expected[k] /= total
+    return [expected[k] for k in meta.policies]
+
+
 def type_policy_tables(model, agent_id, meta: "POTMMCPMetaPolicy", mix) -> N.PomcpTypePolicies:
-    """``pomcp_type_policies`` of a meta-policy over fixed-distribution ego
-    policies and a mixture over fixed-distribution other-agent policies: index
-    order = the dicts' order (what ``random.choice`` / ``random.choices`` see)."""
+    """``pomcp_type_policies`` of a meta-policy over the ego's policies and a
+    mixture over the other agent's: index order = the dicts' order (what
+    ``random.choice`` / ``random.choices`` see).  A state-reactive policy's row
+    is the uniform placeholder nothing draws from; ``other_kinds`` /
+    ``ego_kinds`` say how it acts (``None``: all fixed).  With a reactive ego
+    policy (CooperativeReaching's goal heuristics)
+    ``expected_prior`` is a placeholder too -- the prior of a root is a function
+    of the root -- and ``ego_meta_weights`` carries ``expected_meta_weights``."""
     A = model.action_spaces[agent_id].n
     ego_ids, oth_ids = list(meta.policies), list(mix.policies)
     if len(ego_ids) > N.POMCP_MAX_TYPE_POLICIES or len(oth_ids) > N.POMCP_MAX_TYPE_POLICIES:
         raise NotImplementedError("at most 8 ego and 8 other-agent policies")
+    ego_kinds = ego_policy_kinds(model, agent_id, meta.policies.values(),
+                                 "one of the meta-policy's ego policies")
     tp = N.PomcpTypePolicies()
     tp.num_ego, tp.num_other = len(ego_ids), len(oth_ids)
     for k, pid in enumerate(ego_ids):
-        pi = meta.policies[pid].get_pi({}).probs
+        pi = {a: 1.0 / A for a in range(A)} if is_reactive(meta.policies[pid]) else \
+            meta.policies[pid].get_pi({}).probs
         for a in range(A):
             tp.ego_pi[k][a] = float(pi.get(a, 0.0))
     for j, oid in enumerate(oth_ids):
@@ -190,8 +212,12 @@ def type_policy_tables(model, agent_id, meta: "POTMMCPMetaPolicy", mix) -> N.Pom
         for i, (eid, w) in enumerate(row.items()):
             tp.meta_policy[j][i] = ego_ids.index(eid)
             tp.meta_weight[j][i] = float(w)
-    prior = meta.get_expected_action_probs(None, meta.get_initial_state())
+    # (a heuristic has no action in its initial state: start is None)
+    prior = {a: 1.0 / A for a in range(A)} if ego_kinds else \
+        meta.get_expected_action_probs(None, meta.get_initial_state())
     for a in range(A):
         tp.expected_prior[a] = float(prior[a])
     tp.other_kinds = policy_kinds(model, mix.policies.values())   # (PomcpEngine passes it on)
+    tp.ego_kinds = ego_kinds
+    tp.ego_meta_weights = expected_meta_weights(meta) if ego_kinds else None
     return tp

@@ -13,7 +13,16 @@ terminations), so the Driving-v1 figure is context, not a target.
 Episodes: ``--episode-trees`` x ``--episode-sims`` plain planners, one episode
 each against the population {H1 .. H5}, ``until="all_done"``; the batch's wall
 time per batch step and the device time of its three kernels' groups
-(``pomcp_episodes_timing``)."""
+(``pomcp_episodes_timing``).
+
+``--potmmcp`` measures the type-based search with state-reactive EGO policies
+instead: POTMMCP on CooperativeReaching-v0 ``size=5`` with the
+reference's P0 ``softmax`` meta-policy over the heuristics {H1 .. H5}
+(tests/golden/reactive_ego/p0_meta_policy.json) and the mixture {H1 .. H5},
+beside the same tables with fixed uniform placeholder ego policies, in the same
+process (pucb, ``--potmmcp-trees`` x ``--potmmcp-sims``), and one
+``run_episodes`` batch of ``--episode-trees`` x ``--episode-sims`` such
+planners against {H1 .. H5}."""
 import argparse
 import json
 import math
@@ -32,16 +41,32 @@ CFG = dict(discount=0.95, search_time_limit=0.1, c=math.sqrt(2), truncated=False
 H = [f"CooperativeReaching-v0/H{k}-v0" for k in range(1, 6)]
 
 
-def time_search(model, trees, sims, max_blocks):
+def potmmcp_tables(model, reactive):
+    """The P0 softmax meta-policy's tables over {H1 .. H5} (``reactive``) or over
+    fixed uniform placeholders with the same ids, and the mixture's ids."""
+    from posggym_baselines_amd.planning import OtherAgentMixturePolicy, POTMMCPMetaPolicy
+    from posggym_baselines_amd.planning.policies import FixedDistributionPolicy, GoalHeuristicPolicy
+    from posggym_baselines_amd.planning.potmmcp import type_policy_tables
+    with open(os.path.join(ROOT, "tests", "golden", "reactive_ego", "p0_meta_policy.json")) as f:
+        rows = json.load(f)["meta_policy"]["softmax"]
+    ego = {h: GoalHeuristicPolicy.from_id(model, "0", h) if reactive
+           else FixedDistributionPolicy.uniform(model, "0", h) for h in H}
+    mix = OtherAgentMixturePolicy(model, "1", {h: GoalHeuristicPolicy.from_id(model, "1", h)
+                                               for h in H})
+    meta = POTMMCPMetaPolicy(model, "0", ego, rows)
+    return type_policy_tables(model, "0", meta, mix), list(mix.policies)
+
+
+def time_search(model, trees, sims, max_blocks, cfg_over=None, type_policies=None):
     import torch
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
     from posggym_baselines_amd.planning.engine import plan_capacities
-    cfg = MCTSConfig(seed=0, num_sims=sims, **CFG)
+    cfg = MCTSConfig(seed=0, num_sims=sims, **dict(CFG, **(cfg_over or {})))
     caps = plan_capacities(cfg, model.spec.max_episode_steps, sims, 1, reroot=False,
                            max_blocks=min(max_blocks, sims + 64), overflow_slots=1024)
     stream = torch.cuda.Stream(device=0)
     bp = BatchedPOMCP(model, "0", cfg, trees, sims, capacities=caps, stream=stream.cuda_stream,
-                      defer_cutoff=True, device=0)
+                      defer_cutoff=True, device=0, type_policies=type_policies)
     try:
         bp.init_synthetic(1000)
         with torch.cuda.stream(stream):
@@ -65,13 +90,15 @@ def time_search(model, trees, sims, max_blocks):
     return rec
 
 
-def time_episodes(model, trees, sims, first_seed):
+def time_episodes(model, trees, sims, first_seed, cfg_over=None, type_policies=None,
+                  other_policy_ids=None):
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
     from posggym_baselines_amd.planning.policies import GoalHeuristicPolicy
-    cfg = MCTSConfig(seed=0, num_sims=sims, **CFG)
+    cfg = MCTSConfig(seed=0, num_sims=sims, **dict(CFG, **(cfg_over or {})))
     pop = [GoalHeuristicPolicy.from_id(model, "1", pid) for pid in H]
     steps = model.spec.max_episode_steps
-    bp = BatchedPOMCP(model, "0", cfg, trees, sims, searches=steps, reroot=True)
+    bp = BatchedPOMCP(model, "0", cfg, trees, sims, searches=steps, reroot=True,
+                      type_policies=type_policies, other_policy_ids=other_policy_ids)
     try:
         bp.run_episodes(range(first_seed, first_seed + trees), until="all_done",
                         other_agents=pop)       # the untimed warm-up batch
@@ -98,12 +125,33 @@ def main():
                          "expands up to 1 + 25 + 625 observation nodes)")
     ap.add_argument("--episode-trees", type=int, default=4096)
     ap.add_argument("--episode-sims", type=int, default=256)
+    ap.add_argument("--potmmcp", action="store_true",
+                    help="the type-based search with reactive ego policies (see above)")
+    ap.add_argument("--potmmcp-trees", type=int, default=16384)
+    ap.add_argument("--potmmcp-sims", type=int, default=4096)
     ap.add_argument("--out", default="-")
     args = ap.parse_args()
     import torch
     from posggym_baselines_amd.envs import CooperativeReachingModel, DrivingModel
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     rec = {"device": torch.cuda.get_device_name(0), "search": {}}
+    if args.potmmcp:
+        over = {"action_selection": "pucb", "state_belief_only": False}
+        model = CooperativeReachingModel(size=5)
+        for name, reactive in (("P0 softmax over H1..H5", True), ("fixed placeholders", False)):
+            tp, ids = potmmcp_tables(model, reactive)
+            rec["search"][name] = time_search(model, args.potmmcp_trees, args.potmmcp_sims,
+                                              args.max_blocks, over, tp)
+            print(name, json.dumps(rec["search"][name]), flush=True)
+        tp, ids = potmmcp_tables(model, True)
+        rec["episodes"] = time_episodes(model, args.episode_trees, args.episode_sims, 3000, over,
+                                        tp, ids)
+        print("episodes", json.dumps(rec["episodes"]), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0
     for name, model in (("CooperativeReaching-v0", CooperativeReachingModel()),
                         ("Driving-v1", DrivingModel())):
         rec["search"][name] = time_search(model, args.trees, args.sims, args.max_blocks)
