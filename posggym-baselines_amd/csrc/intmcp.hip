@@ -1349,6 +1349,10 @@ __device__ void im_support(ImPair<Env, NT>& P, int k, ISup* tab, double* prob, u
 // size; the nodes in first-occurrence order over all entries.  Writes tree
 // kt's table `tab` (sizes zeroed) and `prob`, and each particle's slot into .w.
 // (A lane per pair, or the wave's lanes in lockstep on the same pair.)
+// `tab` and `prob` hold Nr entries (entry Nr is the other `sel` table's or the
+// next pair's first): a history that would take slot Nr fails the pair with
+// POMCP_E_ARENA before anything is written for it, every node marked so far is
+// unmarked again, and *nsup = -1 tells the caller to return.
 template <class Env, int NT>
 __device__ void im_support_nested(ImPair<Env, NT>& P, int kB, const ISup* t1, const double* p1, int n1,
                                   uint4* parts1, ISup* tab, double* prob, int* nsup) {
@@ -1362,6 +1366,12 @@ __device__ void im_support_nested(ImPair<Env, NT>& P, int kB, const ISup* t1, co
       const int m = (int)parts1[e.off + i].z;
       int s = (int)P.C(kB, m).support;
       if (P.C(kB, m).support == kImNoSupport) {
+        if (n >= P.p.Nr) {   // one more distinct history than the table holds
+          P.fail(POMCP_E_ARENA);
+          for (int r = 0; r < n; ++r) P.C(kB, tab[r].node).support = kImNoSupport;
+          *nsup = -1;
+          return;
+        }
         s = n++;
         tab[s].node = m;
         tab[s].size = 0;
@@ -1753,6 +1763,7 @@ __device__ void im_update_nestN(ImPair<Env, NT>& P, const typename Env::Model& s
     int n1 = 0;
     if (k == 1) im_support<Env, NT, kWave>(P, 1, t1, pr, P.root_buf(P.h.root_sel), n, &n1);
     else im_support_nested<Env, NT>(P, k, up_t, up_p, up_n, up_q, t1, pr, &n1);
+    if (n1 < 0) return;   // the table is full: the pair has failed, nothing of tree k changes
     if (n1 == 0) {
       P.fail(POMCP_E_STATE);
       return;
@@ -1812,6 +1823,7 @@ __device__ void im_update_nestN(ImPair<Env, NT>& P, const typename Env::Model& s
   ISup* tab = P.sup_tab(sel);
   int n2 = 0;
   im_support_nested<Env, NT>(P, kB, up_t, up_p, up_n, up_q, tab, P.prob, &n2);
+  if (n2 < 0) return;   // (as above)
   if (n2 == 0) {
     P.fail(POMCP_E_STATE);
     return;

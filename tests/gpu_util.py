@@ -209,6 +209,35 @@ def lockstep(bp, env, ego, env_seeds, steps, records, usage=None, after_update=N
         last = actions.astype(np.int32)
 
 
+def node_history(nodes, n, A):
+    """The (action, obs key) path of node n of a device tree (intmcp_get_nodes'
+    records; the None action -> -1): the oracle's OracleINTMCP.history."""
+    out = []
+    while n != 0:
+        a = int(nodes[n]["info"]) & 7
+        out.append((-1 if a == A else a, int(nodes[n]["okey"])))
+        n = int(nodes[n]["parent"])
+    return tuple(reversed(out))
+
+
+def intmcp_device_tables(eng, pair):
+    """The tables of device trees 1 .. max(L, 1) of one pair (the middle trees'
+    intmcp_get_middle_support, the level-0 tree's intmcp_get_support) in the
+    form of oracle_intmcp_limits_pair's "tables"."""
+    L = max(eng.nesting_level, 1)
+    out = []
+    for k in range(1, L + 1):
+        ent, parts = eng.mid_support(pair, k) if k < L else eng.support(pair)
+        nk = eng.nodes(pair, k)
+        below = eng.nodes(pair, k + 1) if k < L else None
+        out.append([(node_history(nk, int(e["node"]), eng.A),
+                     [((int(q[0]), int(q[1])),
+                       node_history(below, int(q[2]), eng.A) if below is not None else None)
+                      for q in parts[int(e["off"]):int(e["off"]) + int(e["size"])]])
+                    for e in ent])
+    return out
+
+
 def intmcp_state_record(eng, pair, searched, action):
     """The oracle's I-NTMCP step record (oracle/run.py oracle_intmcp_record)
     rebuilt from the device state of one planner pair."""
@@ -232,12 +261,7 @@ def intmcp_state_record(eng, pair, searched, action):
     rows = eng.root_belief(pair)
 
     def history(nodes, n):
-        out = []
-        while n != 0:
-            a = int(nodes[n]["info"]) & 7
-            out.append((-1 if a == A else a, int(nodes[n]["okey"])))
-            n = int(nodes[n]["parent"])
-        return tuple(reversed(out))
+        return node_history(nodes, n, A)
 
     def node(nodes, stats, n, ent_, parts_):
         """(visits, registered children, particles) of node n, its particles
@@ -476,7 +500,12 @@ def oracle_intmcp_limits_pair(cfg_kwargs, num_sims, env, nesting_level, pair, en
     tree 1, tree 0 an empty root), "levels": per sample None or, for a search,
     the counts after each search level's simulations, "root_sizes": the root
     belief after each update, "support_series": the materialised particles the
-    largest table needs at each update, "map_need": the obs-child map entries
+    largest table needs at each update, "entry_series": per update, for each
+    device tree k = 1 .. max(L, 1), the histories of the distribution handed to
+    that tree's planner (the entries of its table), "tables": per update and
+    such tree, the table after the update as [(history, [(state words, the
+    history the particle carries in the tree below or None)])] in the
+    distribution's order, "map_need": the obs-child map entries
     per tree at the end, "map_series" / "map_levels": the same at every sample
     and after each search level}.
     last_search=False: the last step ends after its update (no record)."""
@@ -500,18 +529,24 @@ def oracle_intmcp_limits_pair(cfg_kwargs, num_sims, env, nesting_level, pair, en
     target = p.cfg.num_particles + p.cfg.extra_particles
     out["support_series"] = []
 
-    def materialised(pl):
+    out["entry_series"], out["tables"] = [], []
+
+    def materialised(pl, k):
         """The particles of pl's materialised beliefs (the device's support, a
         middle tree's table): the initial beliefs as drawn; at a re-root, per
         history its particles so far and room for a reinvigoration's accepted
-        and rejected samples (csrc/intmcp.hip im_extract_support's cap)."""
+        and rejected samples (csrc/intmcp.hip im_extract_support's cap).  And
+        the entries of device tree k's table: the histories of the distribution
+        the planner is handed."""
         first, later = pl._initial_nested_update, pl._nested_update
 
         def initial(dist):
+            entries[k] = list(dist)
             first(dist)
             needs.append(sum(len(pl.tree.belief[n]) for n in dist))
 
         def update(dist):
+            entries[k] = list(dist)
             need = sum(len(pl.tree.belief[n]) + 2 * math.ceil(pr * target) + 2
                        for n, pr in dist.items())
             needs.append(need)
@@ -519,9 +554,23 @@ def oracle_intmcp_limits_pair(cfg_kwargs, num_sims, env, nesting_level, pair, en
 
         pl._initial_nested_update, pl._nested_update = initial, update
 
-    for pl in (p.planners[:-1] if nesting_level > 0 else p.planners):
-        materialised(pl)
-    nested_sim, levels, map_levels, needs = top._nested_sim, [], [], []
+    tabled = max(nesting_level, 1)     # device trees 1 .. tabled keep a table
+    tabled_planner = {k: by_tree[k] if nesting_level > 0 else by_tree[0] for k in range(1, tabled + 1)}
+    for k, pl in tabled_planner.items():
+        materialised(pl, k)
+
+    def table(k, nodes):
+        """Device tree k's table after the update: per history of the
+        distribution, in its order, (the history, its belief's particles as
+        (state words, the history each carries in the tree below, if any))."""
+        pl = tabled_planner[k]
+        low = pl.nested if pl.level > 0 else None
+        return [(p.history(pl.tree, n),
+                 [(tuple(p.model.pack_words(q[0])),
+                   p.history(low.tree, q[1]) if low is not None else None)
+                  for q in pl.tree.belief[n]]) for n in nodes]
+
+    nested_sim, levels, map_levels, needs, entries = top._nested_sim, [], [], [], {}
 
     def by_level(n, level, top_level):     # the counts when a search level's simulations end
         while len(levels) < level:
@@ -540,8 +589,11 @@ def oracle_intmcp_limits_pair(cfg_kwargs, num_sims, env, nesting_level, pair, en
         if searched:       # OracleINTMCP.step, sampled between its update and its search
             p.stats = {"searched": True}
             del needs[:]
+            entries.clear()
             top.update(top.last_action, obs)
             out["support_series"].append(max(needs))
+            out["entry_series"].append([len(entries.get(k, ())) for k in range(1, tabled + 1)])
+            out["tables"].append([table(k, entries.get(k, ())) for k in range(1, tabled + 1)])
             out["calls"].append((t, "update"))
             out["counts"].append(counts())
             out["levels"].append(None)
@@ -605,14 +657,20 @@ class IntmcpLockstep:
     .root_sizes[b]: its root belief after each of its updates;
     .support_series[b] (support=True): after each of its updates, the largest
       off + cap of its materialised beliefs (intmcp_get_support, and every
-      middle tree's);
+      middle tree's), and .n_entries[b]: the entries of the table of each tree
+      k = 1 .. max(L, 1) (the oracle's "entry_series"; support="entries":
+      these alone, from the pairs' headers);
+    .failed_entries[b] (support=True): the same counts of a pair that failed in
+      an update, read after that call;
+    .tables[b] (pairs in `tables`): after each of its updates, those trees'
+      tables (intmcp_device_tables; the oracle's "tables");
     .scans (scans=True): intmcp_debug_arena_scan's live map slots at the end,
       [pairs][trees].
     last_search=False: the episode ends after the last step's update."""
 
     def __init__(self, cfg_kwargs, num_sims, env_seeds, steps, env="Driving-v1", ego="0",
                  nesting_level=1, capacities=None, record=None, last_search=True, support=False,
-                 scans=False):
+                 scans=False, tables=()):
         import ctypes as C
         import numpy as np
         from oracle.envs import make_model
@@ -635,6 +693,9 @@ class IntmcpLockstep:
             self.records = [[] for _ in range(B)]
             self.root_sizes = [[] for _ in range(B)]
             self.support_series = [[] for _ in range(B)]
+            self.n_entries = [[] for _ in range(B)]
+            self.tables = {b: [] for b in tables}
+            self.failed_entries = {}
             recorded = set(range(B)) if record is None else set(record)
             p32 = C.POINTER(C.c_int32)
 
@@ -649,6 +710,20 @@ class IntmcpLockstep:
                 self.calls.append(dict(step=t, what=what, rc=int(rc), message=bytes(msg).decode(),
                                        counts=counts[:, :trees], errors=errors,
                                        num_sims=np.array([st.num_sims for st in stats])))
+
+            def tabs_of(b):     # the entries of trees 1 .. max(L, 1)
+                return [eng.mid_support(b, k)[0] for k in range(1, eng.nesting_level)] \
+                    + [eng.support(b)[0]]
+
+            def entry_counts(b):     # their number alone: nothing but the pair's header is read
+                ne, npart, out = C.c_int32(), C.c_int32(), []
+                for k in range(1, eng.nesting_level):
+                    assert lib.intmcp_get_middle_support(ctx, b, k, None, 0, C.byref(ne), None, 0,
+                                                         C.byref(npart)) == 0
+                    out.append(int(ne.value))
+                assert lib.intmcp_get_support(ctx, b, None, 0, C.byref(ne), None, 0,
+                                              C.byref(npart)) == 0
+                return out + [int(ne.value)]
 
             envs = []
             for s in env_seeds:
@@ -671,14 +746,20 @@ class IntmcpLockstep:
                                                     keys.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                     absorbing.ctypes.data_as(p32)))
                 for b in range(B):
+                    if support and self.failed.get(b) == len(self.calls) - 1:
+                        self.failed_entries[b] = entry_counts(b)
                     if acts[b] == N.INTMCP_SKIP or b in self.failed:
                         continue
                     self.root_sizes[b].append(int(stats[b].belief_size))
-                    if support:
-                        tabs = [eng.support(b)[0]] + [eng.mid_support(b, k)[0]
-                                                      for k in range(1, eng.nesting_level)]
+                    if support == "entries":
+                        self.n_entries[b].append(entry_counts(b))
+                    elif support:
+                        tabs = tabs_of(b)
                         self.support_series[b].append(max(int(e["off"]) + int(e["cap"])
                                                           for tab in tabs for e in tab))
+                        self.n_entries[b].append([len(tab) for tab in tabs])
+                    if b in self.tables:
+                        self.tables[b].append(intmcp_device_tables(eng, b))
                 if t == steps - 1 and not last_search:
                     break
                 actions = np.zeros(B, dtype=np.int32)
@@ -746,3 +827,37 @@ def oracle_arena_peaks(batch, which):
     for b, x in batch.items():
         peaks[b], trees[b] = max((c[k][which], k) for c in x["counts"] for k in range(len(c)))
     return peaks, trees
+
+
+# The nested history tables at max_root_belief (section f of tests/
+# test_gpu_intmcp_limits.py): (environment, nesting level, simulations per
+# level, first env seed, the largest table of a tree k >= 2, {pair at it:
+# (step of the update that builds it, tree)}) -- pinned on the oracle by
+# tests/test_intmcp_limits_cases.py, which records how they were found.
+IM_TABLE_CASES = (
+    ("PursuitEvasion-v1", 3, 32, 3000, 26, {42: (2, 3)}),
+    ("Driving-v1", 2, 32, 16000, 29, {24: (2, 2)}),
+    ("PursuitEvasion-v1", 3, 32, 5000, 24, {48: (2, 2)}),
+)
+IM_ROOT_BELIEF_FLOOR = 22     # intmcp_create's least max_root_belief: 2 x (num_particles + extra_particles)
+
+
+def nested_table_need(entry_series, root_sizes):
+    """entry_series[b] / root_sizes[b]: pair b's table entries per update and
+    tree k = 1 .. L ("entry_series", IntmcpLockstep.n_entries) and its root
+    belief per update.  Returns (each pair's largest table over the trees k >=
+    2, which im_support_nested fills; the largest of them; {pair at it: (the
+    first update that builds such a table, the first tree -- the update goes
+    top down -- that holds it)}; what max_root_belief needs without those
+    tables: the largest root belief, at least intmcp_create's floor).  A pair
+    updates at every step until its episode ends, so the update's index is its
+    step."""
+    nested = [max((max(e[1:]) for e in es), default=0) for es in entry_series]
+    top = max(nested)
+    tied = {}
+    for b, es in enumerate(entry_series):
+        if nested[b] == top:
+            t = next(t for t, e in enumerate(es) if max(e[1:]) == top)
+            tied[b] = (t, 2 + es[t][1:].index(top))
+    other = max(IM_ROOT_BELIEF_FLOOR, max(max(r, default=0) for r in root_sizes))
+    return nested, top, tied, other

@@ -39,6 +39,10 @@ search level from the failed pair's num_sims):
   im_extract_support .......................... max_support_particles at a re-root
   im_extract_root, a wave per pair ............ max_root_belief, 70 pairs
   im_extract_root, a lane per pair ............ max_root_belief, 1,030 pairs
+  im_support_nested, the level-0 tree ......... max_root_belief at nesting 2 and 3,
+      env seeds chosen so that a nested table is above every root belief
+      (section f); a lane per pair: 1,030 pairs at nesting 3
+  im_support_nested, a middle tree ............ max_root_belief, nesting 3, tree 2
 """
 import functools
 
@@ -46,7 +50,8 @@ import numpy as np
 import pytest
 
 from gpu_util import (IM_LIMITS_CASES, IM_LIMITS_FIRST_SEED, IM_LIMITS_PAIRS, IM_LIMITS_STEPS,
-                      IntmcpLockstep, im_limits_cfg, oracle_intmcp_limits)
+                      IM_TABLE_CASES, IntmcpLockstep, im_limits_cfg, nested_table_need,
+                      oracle_intmcp_limits)
 
 pytestmark = pytest.mark.gpu
 
@@ -169,11 +174,11 @@ def assert_calls(run, base, predicted):
 
 
 # ------------------------------------ b. nodes, log, statistics: full and short
-def one_short(env, nesting, sims, field, base, need, crossing, exp, **kw):
+def one_short(env, nesting, sims, field, base, need, crossing, exp, on_full=None, **kw):
     """The capacity `field` at top = the largest need of a pair, then at top -
     1.  need[b]: pair b's; crossing[b]: the call in which its need passed top -
     1 in the run `base` at planned capacity.  Returns the run one short and
-    the pairs it fails."""
+    the pairs it fails.  on_full: further checks of the run exactly full."""
     top = max(need)
     short_of = [b for b in range(len(need)) if need[b] == top]
     print(field, "top", top, "pairs", short_of, "calls", [crossing[b] for b in short_of])
@@ -188,6 +193,8 @@ def one_short(env, nesting, sims, field, base, need, crossing, exp, **kw):
     assert_records(full, exp, checked)
     for c, c1 in zip(full.calls, base.calls):
         assert (c["counts"] == c1["counts"]).all(), (c["step"], c["what"])
+    if on_full is not None:
+        on_full(full)
 
     short = device(env, nesting, sims, pairs=len(need),
                    capacities=planned(env, nesting, sims, steps, **{field: top - 1}), **kw)
@@ -475,3 +482,136 @@ def test_1030_pairs_root_belief_exactly_full_and_one_short():
     assert max(max(s) for s in first.root_sizes) > 22
     for b, i in short.failed.items():
         assert short.calls[i]["what"] == "update" and short.calls[i]["step"] == 1, b
+
+
+# --------------------------- f. the nested history tables at max_root_belief
+def table_need(run, n):
+    """nested_table_need of a run at planned capacity, and per pair the update
+    call in which a table of a tree k >= 2 first reaches the largest."""
+    nested, top, tied, other = nested_table_need(run.n_entries[:n], run.root_sizes[:n])
+    crossing = [call_index(next((t for t, e in enumerate(es) if max(e[1:]) >= top), 0), "update")
+                for es in run.n_entries[:n]]
+    return nested, top, tied, other, crossing
+
+
+def neighbours(tied, n):
+    """The pairs before and after the pairs of `tied`: entry Nr of a pair's
+    tables and probabilities is entry 0 of the next pair's."""
+    return tuple(sorted({c for b in tied for c in (b - 1, b + 1) if 0 <= c < n and c not in tied}))
+
+
+def assert_tables(run, exp, watch):
+    for b in watch:
+        assert len(run.tables[b]) == len(exp[b]["tables"]), b
+        for t, (got, want) in enumerate(zip(run.tables[b], exp[b]["tables"])):
+            assert got == want, f"pair {b} update {t}: [tree][(history, particles)]"
+
+
+def assert_table_bound(short, base, exp, tied, top, watch):
+    """The run one short of the largest nested table: each pair of `tied` ({pair:
+    (step, tree k)}) fails in that step's update, the tables of its trees above
+    k already this update's and those of tree k and below still the previous
+    update's (the caller returned at once: no selector flipped, no count
+    advanced), no table above the capacity and no counter above its arena;
+    every other pair's table sizes and root beliefs are the planned run's to
+    the end; and the tables of the pairs next to a failed one, read back after
+    every update -- the failing one and those after it -- are the oracle's:
+    histories in order, sizes and particles."""
+    caps = short.capacities
+    assert caps.max_root_belief == top - 1
+    limits = np.array([caps.max_nodes, caps.max_log, caps.max_stats])
+    for b, (t, k) in tied.items():
+        c = short.calls[short.failed[b]]
+        assert (c["what"], c["step"]) == ("update", t), b
+        want = base.n_entries[b][t][:k - 1] + base.n_entries[b][t - 1][k - 1:]
+        print("  pair", b, "fails at step", t, "tree", k, "tables", short.failed_entries[b])
+        assert short.failed_entries[b] == want, b
+        assert max(want) <= top - 1
+        assert short.n_entries[b] == base.n_entries[b][:t], b
+        assert short.root_sizes[b] == base.root_sizes[b][:t], b
+        for c in short.calls:
+            assert (c["counts"][b] <= limits).all(), (b, c["step"], c["what"])
+    for b in range(len(base.n_entries)):
+        if b not in tied:
+            assert short.n_entries[b] == base.n_entries[b], b
+            assert short.root_sizes[b] == base.root_sizes[b], b
+    assert_tables(short, exp, watch)
+
+
+@pytest.mark.parametrize("env,nesting,sims,first,top,tied", IM_TABLE_CASES)
+def test_nested_table_exactly_full_and_one_short(env, nesting, sims, first, top, tied):
+    """At nesting 2 and 3 an update builds, for every tree k >= 2, the table of
+    the distinct histories carried by the particles of tree k - 1's beliefs
+    (im_support_nested), one slot of the pair's [2][Nr] tables and [Nr]
+    probabilities each -- often more histories than the root belief has
+    particles.  The cases (gpu_util.IM_TABLE_CASES, pinned on the oracle by
+    tests/test_intmcp_limits_cases.py) are those whose largest such table is
+    above every root belief and above intmcp_create's floor, so that
+    max_root_belief cut to it is exactly full for that table alone, and one
+    less fails the pairs that hold it in im_support_nested: in the middle-tree
+    loop of im_update_nestN (tree 2 at nesting 3) or at its tail (the level-0
+    tree).  Exactly full, every pair is the oracle's: records, counters, table
+    sizes.  One short: assert_calls and assert_table_bound."""
+    exp = oracle_intmcp_limits(env, nesting, sims, first_seed=first)
+    base = device(env, nesting, sims, first=first, support=True)
+    assert_ok(base)
+    assert_records(base, exp)
+    assert_counts(base, exp)
+    assert base.n_entries == [exp[b]["entry_series"] for b in range(B)]
+    assert base.root_sizes == [exp[b]["root_sizes"] for b in range(B)]
+    assert base.support_series == [exp[b]["support_series"] for b in range(B)]
+    nested, got_top, got_tied, other, crossing = table_need(base, B)
+    print(env, nesting, sims, first, "nested top", got_top, got_tied, "root beliefs and floor", other)
+    assert got_top > other                                   # (a) the table binds, nothing else
+    assert (got_top, got_tied) == (top, tied)                # (b) the pairs the oracle names
+    watch = neighbours(tied, B)
+    assert all(b + 1 in watch for b in tied)
+
+    def full_too(full):
+        assert full.capacities.max_root_belief == top
+        assert full.n_entries == base.n_entries
+        assert_tables(full, exp, watch)
+
+    short, short_of = one_short(env, nesting, sims, "max_root_belief", base, nested, crossing, exp,
+                                on_full=full_too, first=first, support=True, tables=watch)
+    assert short_of == sorted(tied)
+    assert_table_bound(short, base, exp, tied, top, watch)
+
+
+TABLE_BIG = ("Driving-v1", 3, 26, 7000, 3)
+
+
+def test_1030_pairs_nested_table_exactly_full_and_one_short():
+    """im_support_nested in the lane-per-pair update (k_im_updateN<.., false>:
+    more than 1,024 pairs), where a slot past the table is a neighbouring
+    lane's.  1,030 Driving pairs, nesting 3, 26 simulations per level, 3 steps
+    on env seeds 7000 + b (tests/test_intmcp_limits_cases.py records the scan):
+    the need and the tie condition come from the device's own table sizes and
+    root beliefs at planned capacity; the oracle is run on the workgroups of
+    the failing pairs (their successors among them) and the partial last
+    one."""
+    env, nesting, sims, first, steps = TABLE_BIG
+    base = device(env, nesting, sims, pairs=BIG, first=first, steps=steps, record=(),
+                  support="entries")
+    assert_ok(base)
+    nested, top, tied, other, crossing = table_need(base, BIG)
+    print(env, nesting, sims, first, "nested top", top, tied, "root beliefs and floor", other)
+    assert top > other                                       # (a)
+    assert 1 <= len(tied) <= MAX_TIES                        # (b)
+    watch = neighbours(tied, BIG)
+    checked = tuple(sorted(set(big_checked(tied)) | set(watch)))
+    exp = oracle_intmcp_limits(env, nesting, sims, pairs=checked, first_seed=first, steps=steps)
+    for b in checked:
+        assert base.n_entries[b] == exp[b]["entry_series"], b
+        assert base.root_sizes[b] == exp[b]["root_sizes"], b
+
+    def full_too(full):
+        assert full.capacities.max_root_belief == top
+        assert full.n_entries == base.n_entries
+        assert_tables(full, exp, watch)
+
+    short, short_of = one_short(env, nesting, sims, "max_root_belief", base, nested, crossing, exp,
+                                on_full=full_too, first=first, steps=steps, record=checked,
+                                support="entries", tables=watch)
+    assert short_of == sorted(tied)
+    assert_table_bound(short, base, exp, tied, top, watch)
