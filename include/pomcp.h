@@ -43,8 +43,10 @@ typedef enum pomcp_selection {
 typedef enum pomcp_env {
   POMCP_ENV_DRIVING = 1,            /* Driving-v1: pomcp_config.grid */
   POMCP_ENV_PURSUIT_EVASION = 2,    /* PursuitEvasion-v1: pomcp_config.pe_grid */
-  POMCP_ENV_COOPERATIVE_REACHING = 3   /* CooperativeReaching-v0: a pomcp_cr_grid beside the
+  POMCP_ENV_COOPERATIVE_REACHING = 3,  /* CooperativeReaching-v0: a pomcp_cr_grid beside the
                                           config (pomcp_create_env) */
+  POMCP_ENV_PREDATOR_PREY = 4          /* PredatorPrey-v0: a pomcp_pp_grid beside the config
+                                          (pomcp_create_env) */
 } pomcp_env;
 
 /* Driving-v1 grid tables (16-wide row stride). */
@@ -77,6 +79,18 @@ typedef struct pomcp_cr_grid {
   uint8_t goal[4][2];             /* one per corner */
   double goal_value[4];           /* the reward of both agents on goal k */
 } pomcp_cr_grid;
+
+/* PredatorPrey-v0 (csrc/predator_prey.h): two predators and num_prey prey on an
+ * open S x S grid; coordinates are (x, y). */
+typedef struct pomcp_pp_grid {
+  int32_t size;                   /* S: 5 or 10 */
+  int32_t num_prey;               /* 1..3 */
+  int32_t prey_strength;          /* predators beside a prey that catch it: 1..2 */
+  int32_t obs_dim;                /* the observation window reaches this far: 1..2 */
+  uint8_t start[8][2];            /* the predators' start cells in row-major order: the
+                                     corners and the edge cells at x or y = S / 2 */
+  double capture_reward;          /* (double)(float)(1.0 / num_prey), per prey caught */
+} pomcp_pp_grid;
 
 /* MCTSConfig (config.py:8-55) after __post_init__, plus engine sizing. */
 typedef struct pomcp_config {
@@ -160,9 +174,10 @@ int32_t pomcp_abi_version(void);
 int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomcp_ctx** out);
 /* pomcp_create for an environment whose description travels beside the config
  * (ABI 7, additive; pomcp_config does not grow): POMCP_ENV_COOPERATIVE_REACHING,
- * env_desc its pomcp_cr_grid and env_desc_bytes that struct's sizeof.
- * pomcp_create refuses that env_id, and this call every other
- * (POMCP_E_UNSUPPORTED).  The environment runs the tree-per-lane search only
+ * env_desc its pomcp_cr_grid and env_desc_bytes that struct's sizeof, or
+ * POMCP_ENV_PREDATOR_PREY with its pomcp_pp_grid.
+ * pomcp_create refuses those env_ids, and this call every other
+ * (POMCP_E_UNSUPPORTED).  These environments run the tree-per-lane search only
  * (pomcp_set_search_kernel(POMCP_SEARCH_WAVE): POMCP_E_UNSUPPORTED). */
 int pomcp_create_env(const pomcp_config* cfg, const void* env_desc, int64_t env_desc_bytes,
                      int32_t device, void* hip_stream, pomcp_ctx** out);
@@ -437,6 +452,20 @@ int pomcp_cr_sample_agent_initial_state(const pomcp_cr_grid* g, int32_t agent, u
                                         uint64_t seed, uint32_t tree, uint32_t* model_ctr,
                                         uint32_t state_out[2]);
 
+/* ---- Host (CPU) PredatorPrey-v0 model from csrc/predator_prey.h */
+int pomcp_pp_sample_initial_state(const pomcp_pp_grid* g, uint64_t seed, uint32_t tree,
+                                  uint32_t* model_ctr, uint32_t state_out[2]);
+/* One joint step: one draw in [0, 2^25) of the model stream at *model_ctr (the
+ * prey's tie bytes and the predators' order). */
+int pomcp_pp_step(const pomcp_pp_grid* g, const uint32_t state[2], const int32_t actions[2],
+                  uint64_t seed, uint32_t tree, uint32_t* model_ctr, uint32_t next_out[2],
+                  double rewards_out[2], int32_t terminated_out[2], uint64_t obs_keys_out[2]);
+int pomcp_pp_obs(const pomcp_pp_grid* g, const uint32_t state[2], uint64_t obs_keys_out[2]);
+/* model.sample_agent_initial_state(agent, obs) with the model stream at
+ * *model_ctr; POMCP_E_INVALID for an observation outside the model. */
+int pomcp_pp_sample_agent_initial_state(const pomcp_pp_grid* g, int32_t agent, uint64_t obs_key,
+                                        uint64_t seed, uint32_t tree, uint32_t* model_ctr,
+                                        uint32_t state_out[2]);
 /* ---- Host RNG streams (csrc/philox.h) -----------------------------------
  * out[k] = word (first + k) of Philox stream `stream` under key (seed, tree):
  * the draws of the episode loop's non-planning agents (the reference's
@@ -557,8 +586,9 @@ int pomcp_episodes_timing(pomcp_ctx* ctx, double ms[3], int32_t* steps);
 
 /* ---- Host twin of the per-tree episode step (csrc/episode_step.h) ----------
  * The code k_episode_reset / k_episode_step run per tree, on the host.
- * grid: a pomcp_grid (env_id POMCP_ENV_DRIVING), a pomcp_pe_grid or a
- * pomcp_cr_grid (POMCP_ENV_COOPERATIVE_REACHING). */
+ * grid: a pomcp_grid (env_id POMCP_ENV_DRIVING), a pomcp_pe_grid, a
+ * pomcp_cr_grid (POMCP_ENV_COOPERATIVE_REACHING) or a pomcp_pp_grid
+ * (POMCP_ENV_PREDATOR_PREY). */
 int pomcp_host_episode_reset(int32_t env_id, const void* grid, int32_t ego, uint64_t env_seed,
                              pomcp_episode_state* st, uint64_t* obs_key_out);
 int pomcp_host_episode_step(int32_t env_id, const void* grid, int32_t ego,

@@ -101,6 +101,16 @@ int pomcp_debug_log_drop(pomcp_ctx* ctx, const uint64_t* masks);
  * high words, 0}.  The ego is the context's.  States must be ones the model
  * produces (a Driving vehicle's min-distance field at most its cell's distance). */
 int pomcp_debug_env_step(pomcp_ctx* ctx, const uint32_t* in, int32_t n, uint32_t* out);
+/* Host: pomcp_pp_step (pomcp.h) with the draw given (j < 2^25) instead of taken
+ * from a stream, and what the step did, for the tests' conditions: rules_out[k]
+ * the rule that decided prey k's move (0 a predator, 1 another prey, 2 neither;
+ * -1 not live), blocked_out[i] whether predator i's move was held in place.
+ * Either may be NULL. */
+int pomcp_debug_pp_step_draw(const pomcp_pp_grid* g, const uint32_t state[2],
+                             const int32_t actions[2], uint32_t j, uint32_t next_out[2],
+                             double rewards_out[2], int32_t terminated_out[2],
+                             uint64_t obs_keys_out[2], int32_t rules_out[3],
+                             int32_t blocked_out[2]);
 #ifdef __cplusplus
 }
 #endif

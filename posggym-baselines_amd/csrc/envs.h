@@ -4,7 +4,11 @@
 //   Model                      device tables (staged in LDS)
 //   kStepDraws                 model-stream draws per joint step (Driving's
 //                              execution-order shuffle: 1; PursuitEvasion,
-//                              CooperativeReaching: 0)
+//                              CooperativeReaching: 0; PredatorPrey's tie
+//                              bytes and order bit: 1)
+//   kStepRange                 that draw is uniform_int(word, kStepRange)
+//                              (Driving 2, PredatorPrey 2^25; unused at
+//                              kStepDraws 0)
 //   step(m, ego, s0, s1, a_ego, a_oth, j, &n0, &n1, &r, &done)
 //                              joint step + the ego's reward and
 //                              terminated-or-all-done flag (mcts.py:333-344)
@@ -29,6 +33,7 @@
 #include "driving.h"
 #include "driving_policy.h"
 #include "driving_vec.h"
+#include "predator_prey.h"
 #include "pursuit_evasion.h"
 
 namespace pb {
@@ -36,6 +41,7 @@ namespace pb {
 struct EnvDriving {
   using Model = DrvModel;
   static constexpr int kStepDraws = 1;
+  static constexpr uint32_t kStepRange = 2u;
   static constexpr int kEnvId = POMCP_ENV_DRIVING;
   static constexpr int kA = 5;   // actions per agent
   static constexpr bool kEgoKinds = false;   // (the ego's own word depends on hidden actions)
@@ -96,6 +102,7 @@ struct EnvDriving {
 struct EnvPursuitEvasion {
   using Model = PeModel;
   static constexpr int kStepDraws = 0;
+  static constexpr uint32_t kStepRange = 1u;
   static constexpr int kEnvId = POMCP_ENV_PURSUIT_EVASION;
   static constexpr int kA = 4;   // actions per agent
   static constexpr bool kEgoKinds = false;
@@ -134,6 +141,7 @@ struct EnvPursuitEvasion {
 struct EnvCoopReaching {
   using Model = CrModel;
   static constexpr int kStepDraws = 0;
+  static constexpr uint32_t kStepRange = 1u;
   static constexpr int kEnvId = POMCP_ENV_COOPERATIVE_REACHING;
   static constexpr int kA = 5;   // actions per agent
   static constexpr bool kEgoKinds = true;   // POMCP_POLICY_CR_GOAL as an ego policy (§22)
@@ -167,6 +175,45 @@ struct EnvCoopReaching {
   __device__ static bool sample_agent_initial(const Model& m, int ego, uint64_t obs, Draw draw,
                                               uint32_t* s0, uint32_t* s1) {
     return cr_sample_agent_initial(m, ego, obs, draw, s0, s1);
+  }
+};
+
+struct EnvPredatorPrey {
+  using Model = PpModel;
+  static constexpr int kStepDraws = 1;
+  static constexpr uint32_t kStepRange = kPpStepRange;   // three tie bytes and the order bit
+  static constexpr int kEnvId = POMCP_ENV_PREDATOR_PREY;
+  static constexpr int kA = 5;   // actions per agent
+  static constexpr bool kEgoKinds = false;
+
+  // (straight-line on the VALU, predator_prey.h: the prey's candidates a 5-bit
+  // mask, the choice by popcount and k-th set bit; the only model reads are
+  // its scalars)
+  __device__ static __forceinline__ void step(const Model& m, int ego, uint32_t s0, uint32_t s1,
+                                              uint32_t a_ego, uint32_t a_oth, uint32_t j,
+                                              uint32_t* n0, uint32_t* n1, double* r, int* done) {
+    pp_step(m, s0, s1, ego == 0 ? a_ego : a_oth, ego == 0 ? a_oth : a_ego, j, n0, n1, r);
+    *done = done_of(ego, *n0, *n1);
+  }
+  __device__ static __forceinline__ int done_of(int /*ego*/, uint32_t n0, uint32_t /*n1*/) {
+    return pp_done(n0) ? 1 : 0;   // both agents terminate together
+  }
+  __device__ static __forceinline__ uint64_t obs_key(const Model& m, int ego, uint32_t n0,
+                                                     uint32_t n1) {
+    return pp_obs_key(m, ego, n0, n1);
+  }
+  __device__ static __forceinline__ uint32_t policy_action(const Model&, int, uint32_t, uint32_t,
+                                                           int, int, int) {
+    return 0u;   // (no reactive kinds: pomcp_set_type_policy_kinds refuses them)
+  }
+  template <class Draw>
+  __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
+    pp_sample_initial_state(m, draw, s0, s1);
+  }
+  template <class Draw>
+  __device__ static bool sample_agent_initial(const Model& m, int ego, uint64_t obs, Draw draw,
+                                              uint32_t* s0, uint32_t* s1) {
+    return pp_sample_agent_initial(m, ego, obs, draw, s0, s1);
   }
 };
 

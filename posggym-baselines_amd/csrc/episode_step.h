@@ -31,6 +31,7 @@
 #include "driving.h"
 #include "driving_policy.h"
 #include "philox.h"
+#include "predator_prey.h"
 #include "pursuit_evasion.h"
 #include "../../include/pomcp.h"
 
@@ -117,6 +118,31 @@ struct EpCoopReaching {
                                  int p0, int /*p1*/) {
     return cr_goal_action(m, agent == 0 ? s0 : s1, p0);
   }
+};
+
+struct EpPredatorPrey {
+  using Model = PpModel;
+  static constexpr uint32_t kA = 5;
+  static constexpr uint32_t kStepRange = kPpStepRange;
+  template <class Draw>
+  PB_HD static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
+    pp_sample_initial_state(m, draw, s0, s1);
+  }
+  // pomcp_pp_step: the prey's tie bytes and the predators' order are one model
+  // draw; one reward for both, both terminate together
+  PB_HD static void step(const Model& m, Streams& env, uint32_t s0, uint32_t s1, int a0, int a1,
+                         uint32_t* n0, uint32_t* n1, double r[2], int term[2]) {
+    const uint32_t j = env.model(kStepRange);
+    pp_step(m, s0, s1, (uint32_t)a0, (uint32_t)a1, j, n0, n1, &r[0]);
+    r[1] = r[0];
+    term[0] = term[1] = pp_done(*n0) ? 1 : 0;
+  }
+  PB_HD static uint64_t obs_key(const Model& m, int agent, uint32_t n0, uint32_t n1) {
+    return pp_obs_key(m, agent, n0, n1);
+  }
+  // (no reactive kinds: a population with one is refused before it gets here)
+  PB_HD static bool has_kind(int /*kind*/) { return false; }
+  PB_HD static int policy_action(const Model&, int, uint32_t, uint32_t, int, int, int) { return 0; }
 };
 
 // kind / parameters of one policy of a population or a mixture

@@ -35,6 +35,7 @@
 #include "host_exp.h"
 #include "intmcp_episode.h"
 #include "philox.h"
+#include "predator_prey.h"
 #include "pursuit_evasion.h"
 #include "tm_prior.h"
 #include "../../include/pomcp.h"
@@ -70,6 +71,10 @@ void with_host_env(int32_t env_id, const void* grid, F&& f) {
     PeModel m;
     build_pe_model(*reinterpret_cast<const pomcp_pe_grid*>(grid), &m);
     f(EpPursuitEvasion{}, m);
+  } else if (env_id == POMCP_ENV_PREDATOR_PREY) {
+    PpModel m;
+    build_pp_model(*reinterpret_cast<const pomcp_pp_grid*>(grid), &m);
+    f(EpPredatorPrey{}, m);
   } else {
     CrModel m;
     build_cr_model(*reinterpret_cast<const pomcp_cr_grid*>(grid), &m);
@@ -266,6 +271,93 @@ int pomcp_host_cr_prior_lines(const pomcp_cr_grid* g, int32_t num_ego, const dou
   return POMCP_OK;
 }
 
+// ------------------------------------------------------- host PredatorPrey
+
+namespace {
+Streams pp_streams(uint64_t seed, uint32_t tree, uint32_t model_ctr) {
+  Streams s;
+  s.seed = seed;
+  s.tree = tree;
+  for (int k = 0; k < 5; ++k) s.ctr[k] = 0;
+  s.ctr[2] = model_ctr;
+  return s;
+}
+}  // namespace
+
+int pomcp_pp_sample_initial_state(const pomcp_pp_grid* g, uint64_t seed, uint32_t tree,
+                                  uint32_t* model_ctr, uint32_t state_out[2]) {
+  if (!g || !model_ctr || !state_out || !pp_grid_ok(*g)) return POMCP_E_INVALID;
+  PpModel m;
+  build_pp_model(*g, &m);
+  Streams s = pp_streams(seed, tree, *model_ctr);
+  pp_sample_initial_state(m, [&](uint32_t n) { return s.model(n); }, &state_out[0], &state_out[1]);
+  *model_ctr = s.ctr[2];
+  return POMCP_OK;
+}
+
+int pomcp_pp_sample_agent_initial_state(const pomcp_pp_grid* g, int32_t agent, uint64_t obs_key,
+                                        uint64_t seed, uint32_t tree, uint32_t* model_ctr,
+                                        uint32_t state_out[2]) {
+  if (!g || !model_ctr || !state_out || (agent != 0 && agent != 1) || !pp_grid_ok(*g))
+    return POMCP_E_INVALID;
+  PpModel m;
+  build_pp_model(*g, &m);
+  Streams s = pp_streams(seed, tree, *model_ctr);
+  const bool ok = pp_sample_agent_initial(m, agent, obs_key, [&](uint32_t n) { return s.model(n); },
+                                          &state_out[0], &state_out[1]);
+  *model_ctr = s.ctr[2];
+  return ok ? POMCP_OK : POMCP_E_INVALID;
+}
+
+// (pomcp_debug.h: the step with the draw given, and what it did)
+int pomcp_debug_pp_step_draw(const pomcp_pp_grid* g, const uint32_t state[2],
+                             const int32_t actions[2], uint32_t j, uint32_t next_out[2],
+                             double rewards_out[2], int32_t terminated_out[2],
+                             uint64_t obs_keys_out[2], int32_t rules_out[3],
+                             int32_t blocked_out[2]) {
+  if (!g || !state || !actions || !next_out || !rewards_out || !terminated_out || !obs_keys_out ||
+      !pp_grid_ok(*g) || j >= kPpStepRange)
+    return POMCP_E_INVALID;
+  for (int i = 0; i < 2; ++i)
+    if (actions[i] < 0 || actions[i] > 4) return POMCP_E_INVALID;
+  PpModel m;
+  build_pp_model(*g, &m);
+  if (!pp_state_ok(m, state)) return POMCP_E_INVALID;
+  uint32_t n;
+  PpStepInfo info;
+  pp_step_info(m, state[0], state[1], (uint32_t)actions[0], (uint32_t)actions[1], j, &next_out[0],
+               &next_out[1], &n, &info);
+  for (int i = 0; i < 2; ++i) {
+    rewards_out[i] = (double)n * m.reward;
+    terminated_out[i] = pp_done(next_out[0]) ? 1 : 0;
+    obs_keys_out[i] = pp_obs_key(m, i, next_out[0], next_out[1]);
+    if (blocked_out) blocked_out[i] = info.blocked[i];
+  }
+  for (int k = 0; rules_out && k < kPpMaxPrey; ++k) rules_out[k] = info.rule[k];
+  return POMCP_OK;
+}
+
+int pomcp_pp_step(const pomcp_pp_grid* g, const uint32_t state[2], const int32_t actions[2],
+                  uint64_t seed, uint32_t tree, uint32_t* model_ctr, uint32_t next_out[2],
+                  double rewards_out[2], int32_t terminated_out[2], uint64_t obs_keys_out[2]) {
+  if (!model_ctr) return POMCP_E_INVALID;
+  Streams s = pp_streams(seed, tree, *model_ctr);
+  const uint32_t j = s.model(kPpStepRange);
+  const int rc = pomcp_debug_pp_step_draw(g, state, actions, j, next_out, rewards_out,
+                                          terminated_out, obs_keys_out, nullptr, nullptr);
+  if (rc == POMCP_OK) *model_ctr = s.ctr[2];
+  return rc;
+}
+
+int pomcp_pp_obs(const pomcp_pp_grid* g, const uint32_t state[2], uint64_t obs_keys_out[2]) {
+  if (!g || !state || !obs_keys_out || !pp_grid_ok(*g)) return POMCP_E_INVALID;
+  PpModel m;
+  build_pp_model(*g, &m);
+  if (!pp_state_ok(m, state)) return POMCP_E_INVALID;
+  for (int i = 0; i < 2; ++i) obs_keys_out[i] = pp_obs_key(m, i, state[0], state[1]);
+  return POMCP_OK;
+}
+
 // ---------------------------------------------------------- host RNG streams
 
 int pomcp_philox_words(uint64_t seed, uint32_t tree, uint32_t stream, uint32_t first, int32_t n,
@@ -374,6 +466,8 @@ bool episode_env_ok(int32_t env_id, const void* grid, int32_t ego) {
   if (grid == nullptr || (ego != 0 && ego != 1)) return false;
   if (env_id == POMCP_ENV_COOPERATIVE_REACHING)
     return cr_grid_ok(*reinterpret_cast<const pomcp_cr_grid*>(grid));
+  if (env_id == POMCP_ENV_PREDATOR_PREY)
+    return pp_grid_ok(*reinterpret_cast<const pomcp_pp_grid*>(grid));
   return env_id == POMCP_ENV_DRIVING || env_id == POMCP_ENV_PURSUIT_EVASION;
 }
 

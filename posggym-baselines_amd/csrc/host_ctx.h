@@ -36,6 +36,7 @@ struct __attribute__((visibility("hidden"))) HostCtx {
   DrvModel host_drv;      // the configured environment's device tables
   PeModel host_pe;
   CrModel host_cr;
+  PpModel host_pp;
   const void* host_model = nullptr;
   size_t model_bytes = 0;
 
@@ -64,11 +65,16 @@ struct __attribute__((visibility("hidden"))) HostCtx {
     stream = nullptr;
   }
 
-  // (cr: the description a POMCP_ENV_COOPERATIVE_REACHING context is created
-  // with, pomcp_create_env; the other environments' travel in the config)
-  void set_env_model(const pomcp_config& c, const pomcp_cr_grid* cr = nullptr) {
-    if (c.env_id == POMCP_ENV_COOPERATIVE_REACHING) {
-      build_cr_model(*cr, &host_cr);
+  // (desc: the description a POMCP_ENV_COOPERATIVE_REACHING (pomcp_cr_grid) or
+  // POMCP_ENV_PREDATOR_PREY (pomcp_pp_grid) context is created with,
+  // pomcp_create_env; the other environments' travel in the config)
+  void set_env_model(const pomcp_config& c, const void* desc = nullptr) {
+    if (c.env_id == POMCP_ENV_PREDATOR_PREY) {
+      build_pp_model(*static_cast<const pomcp_pp_grid*>(desc), &host_pp);
+      host_model = &host_pp;
+      model_bytes = sizeof(PpModel);
+    } else if (c.env_id == POMCP_ENV_COOPERATIVE_REACHING) {
+      build_cr_model(*static_cast<const pomcp_cr_grid*>(desc), &host_cr);
       host_model = &host_cr;
       model_bytes = sizeof(CrModel);
     } else if (c.env_id == POMCP_ENV_PURSUIT_EVASION) {
@@ -154,14 +160,17 @@ template <class Drv, class Pe, class F>
 static void env_dispatch(int32_t env, F&& f) {
   dispatch<Drv, Pe>(env == POMCP_ENV_PURSUIT_EVASION ? 1 : 0, f);
 }
-// the row of a pomcp_env in a table of kernels: Driving, PursuitEvasion, CooperativeReaching
+// the row of a pomcp_env in a table of kernels: Driving, PursuitEvasion,
+// CooperativeReaching, PredatorPrey
 static inline int env_row(int32_t env) {
-  return env == POMCP_ENV_COOPERATIVE_REACHING ? 2 : (env == POMCP_ENV_PURSUIT_EVASION ? 1 : 0);
+  return env == POMCP_ENV_PREDATOR_PREY
+             ? 3
+             : (env == POMCP_ENV_COOPERATIVE_REACHING ? 2 : (env == POMCP_ENV_PURSUIT_EVASION ? 1 : 0));
 }
-// the same with f(Cr{}): the layers that run all three environments
-template <class Drv, class Pe, class Cr, class F>
-static void env_dispatch3(int32_t env, F&& f) {
-  dispatch<Drv, Pe, Cr>(env_row(env), f);
+// the same with f(Cr{}) and f(Pp{}): the layers that run all four environments
+template <class Drv, class Pe, class Cr, class Pp, class F>
+static void env_dispatch4(int32_t env, F&& f) {
+  dispatch<Drv, Pe, Cr, Pp>(env_row(env), f);
 }
 
 }  // namespace pb

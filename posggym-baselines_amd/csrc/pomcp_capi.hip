@@ -120,13 +120,13 @@ constexpr int kStepTreeMaxDepth = 8;
 // f(Env{}) with the context's environment (envs.h)
 template <class F>
 static void with_env(const pomcp_ctx* ctx, F&& f) {
-  env_dispatch3<EnvDriving, EnvPursuitEvasion, EnvCoopReaching>(ctx->dp.env, f);
+  env_dispatch4<EnvDriving, EnvPursuitEvasion, EnvCoopReaching, EnvPredatorPrey>(ctx->dp.env, f);
 }
 
 // f(Env{}) with the context's environment as the episode kernels know it (episode_step.h)
 template <class F>
 static void with_episode_env(const pomcp_ctx* ctx, F&& f) {
-  env_dispatch3<EpDriving, EpPursuitEvasion, EpCoopReaching>(ctx->dp.env, f);
+  env_dispatch4<EpDriving, EpPursuitEvasion, EpCoopReaching, EpPredatorPrey>(ctx->dp.env, f);
 }
 
 // The first tree whose status code(t) is an error, named by its kind.
@@ -167,8 +167,10 @@ int pomcp_set_stream(pomcp_ctx* ctx, void* hip_stream) {
   return POMCP_OK;
 }
 
-// (cr: the description beside the config, pomcp_create_env; null from pomcp_create)
-static int validate(const pomcp_config* c, const pomcp_cr_grid* cr, std::string* why) {
+// (desc: the description beside the config, pomcp_create_env (the env_id's
+// struct, its size checked there); null from pomcp_create)
+static int validate(const pomcp_config* c, const void* desc, std::string* why) {
+  const pomcp_cr_grid* cr = static_cast<const pomcp_cr_grid*>(desc);
   auto bad = [&](const char* m) {
     *why = m;
     return POMCP_E_INVALID;
@@ -178,15 +180,22 @@ static int validate(const pomcp_config* c, const pomcp_cr_grid* cr, std::string*
     *why = "env_id: CooperativeReaching-v0 takes its pomcp_cr_grid through pomcp_create_env";
     return POMCP_E_UNSUPPORTED;
   }
+  if (c->env_id == POMCP_ENV_PREDATOR_PREY && desc == nullptr) {
+    *why = "env_id: PredatorPrey-v0 takes its pomcp_pp_grid through pomcp_create_env";
+    return POMCP_E_UNSUPPORTED;
+  }
   if (c->env_id != POMCP_ENV_DRIVING && c->env_id != POMCP_ENV_PURSUIT_EVASION &&
-      c->env_id != POMCP_ENV_COOPERATIVE_REACHING) {
-    *why = "env_id: Driving-v1, PursuitEvasion-v1 or CooperativeReaching-v0";
+      c->env_id != POMCP_ENV_COOPERATIVE_REACHING && c->env_id != POMCP_ENV_PREDATOR_PREY) {
+    *why = "env_id: Driving-v1, PursuitEvasion-v1, CooperativeReaching-v0 or PredatorPrey-v0";
     return POMCP_E_UNSUPPORTED;
   }
   if (c->num_agents != 2) { *why = "the engine's models are 2-agent"; return POMCP_E_UNSUPPORTED; }
   if (c->num_actions != (c->env_id == POMCP_ENV_PURSUIT_EVASION ? 4 : 5)) return bad("num_actions of the model");
   if (c->env_id == POMCP_ENV_COOPERATIVE_REACHING && !cr_grid_ok(*cr))
     return bad("cr grid: size 3..8, four corner goals, obs_distance -1..7");
+  if (c->env_id == POMCP_ENV_PREDATOR_PREY && !pp_grid_ok(*static_cast<const pomcp_pp_grid*>(desc)))
+    return bad("pp grid: size 5 or 10, 1..3 prey, prey_strength 1..2, obs_dim 1..2, the start "
+               "cells and the capture reward of the model");
   if (c->env_id == POMCP_ENV_PURSUIT_EVASION) {
     const pomcp_pe_grid& g = c->pe_grid;
     if (g.width < 1 || g.width > 16 || g.height < 1 || g.height > 16) return bad("pe grid size");
@@ -235,8 +244,8 @@ static int validate(const pomcp_config* c, const pomcp_cr_grid* cr, std::string*
   return POMCP_OK;
 }
 
-static int create_ctx(const pomcp_config* cfg, const pomcp_cr_grid* cr, int32_t device,
-                      void* hip_stream, pomcp_ctx** out);
+static int create_ctx(const pomcp_config* cfg, const void* desc, int32_t device, void* hip_stream,
+                      pomcp_ctx** out);
 
 int pomcp_create(const pomcp_config* cfg, int32_t device, void* hip_stream, pomcp_ctx** out) {
   return create_ctx(cfg, nullptr, device, hip_stream, out);
@@ -247,17 +256,20 @@ int pomcp_create_env(const pomcp_config* cfg, const void* env_desc, int64_t env_
   if (!cfg || !out || !env_desc) return POMCP_E_INVALID;
   *out = nullptr;
   // (the other environments' descriptions have their place in the config: pomcp_create)
-  if (cfg->env_id != POMCP_ENV_COOPERATIVE_REACHING) return POMCP_E_UNSUPPORTED;
-  if (env_desc_bytes != (int64_t)sizeof(pomcp_cr_grid)) return POMCP_E_INVALID;
-  return create_ctx(cfg, static_cast<const pomcp_cr_grid*>(env_desc), device, hip_stream, out);
+  if (cfg->env_id != POMCP_ENV_COOPERATIVE_REACHING && cfg->env_id != POMCP_ENV_PREDATOR_PREY)
+    return POMCP_E_UNSUPPORTED;
+  const int64_t want = cfg->env_id == POMCP_ENV_PREDATOR_PREY ? (int64_t)sizeof(pomcp_pp_grid)
+                                                              : (int64_t)sizeof(pomcp_cr_grid);
+  if (env_desc_bytes != want) return POMCP_E_INVALID;
+  return create_ctx(cfg, env_desc, device, hip_stream, out);
 }
 
-static int create_ctx(const pomcp_config* cfg, const pomcp_cr_grid* cr, int32_t device,
-                      void* hip_stream, pomcp_ctx** out) {
+static int create_ctx(const pomcp_config* cfg, const void* desc, int32_t device, void* hip_stream,
+                      pomcp_ctx** out) {
   if (!cfg || !out) return POMCP_E_INVALID;
   *out = nullptr;
   std::string why;
-  int rc = validate(cfg, cr, &why);
+  int rc = validate(cfg, desc, &why);
   if (rc != POMCP_OK) {
     std::fprintf(stderr, "pomcp_create: %s\n", why.c_str());
     return rc;
@@ -269,7 +281,7 @@ static int create_ctx(const pomcp_config* cfg, const pomcp_cr_grid* cr, int32_t 
     return rc;
   }
   const pomcp_config& c = *cfg;
-  ctx->set_env_model(c, cr);
+  ctx->set_env_model(c, desc);
   DevParams& d = ctx->dp;
   d.env = c.env_id;
   d.B = c.num_trees;
@@ -441,7 +453,8 @@ static int ensure_compaction_scratch(pomcp_ctx* ctx) {
   int per_cu = 0, ncu = 0;
   PB_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(
                   &per_cu, reinterpret_cast<const void*>(
-                               d.env == POMCP_ENV_COOPERATIVE_REACHING ? &k_log_filter<EnvCoopReaching>
+                               d.env == POMCP_ENV_PREDATOR_PREY        ? &k_log_filter<EnvPredatorPrey>
+                               : d.env == POMCP_ENV_COOPERATIVE_REACHING ? &k_log_filter<EnvCoopReaching>
                                : d.env == POMCP_ENV_PURSUIT_EVASION    ? &k_log_filter<EnvPursuitEvasion>
                                                                        : &k_log_filter<EnvDriving>),
                   kLfThreads, 0));
@@ -539,9 +552,12 @@ int pomcp_update(pomcp_ctx* ctx, const int32_t* actions, const uint64_t* obs_key
   return first_update_error(ctx);
 }
 
-// (CooperativeReaching-v0 runs the tree-per-lane kernel only)
+// (CooperativeReaching-v0 and PredatorPrey-v0 run the tree-per-lane kernel only)
+static bool lane_only_env(int32_t env) {
+  return env == POMCP_ENV_COOPERATIVE_REACHING || env == POMCP_ENV_PREDATOR_PREY;
+}
 static bool wave_search_fits(const pomcp_ctx* ctx) {
-  return ctx->dp.env != POMCP_ENV_COOPERATIVE_REACHING && ctx->dp.A <= kMaxA &&
+  return !lane_only_env(ctx->dp.env) && ctx->dp.A <= kMaxA &&
          (int64_t)ctx->dp.B * ctx->dp.Np * (int64_t)sizeof(LogRec) <= kWaveSearchMaxScratch;
 }
 
@@ -555,9 +571,11 @@ static int resolve_search_kind(const pomcp_ctx* ctx) {
 
 int pomcp_set_search_kernel(pomcp_ctx* ctx, int32_t kind) {
   if (!ctx || kind < POMCP_SEARCH_AUTO || kind > POMCP_SEARCH_WAVE) return POMCP_E_INVALID;
-  if (kind == POMCP_SEARCH_WAVE && ctx->dp.env == POMCP_ENV_COOPERATIVE_REACHING)
-    return fail(ctx, POMCP_E_UNSUPPORTED, "set_search_kernel: CooperativeReaching-v0 has no "
-                                          "wave-per-tree search");
+  if (kind == POMCP_SEARCH_WAVE && lane_only_env(ctx->dp.env))
+    return fail(ctx, POMCP_E_UNSUPPORTED,
+                ctx->dp.env == POMCP_ENV_PREDATOR_PREY
+                    ? "set_search_kernel: PredatorPrey-v0 has no wave-per-tree search"
+                    : "set_search_kernel: CooperativeReaching-v0 has no wave-per-tree search");
   if (kind == POMCP_SEARCH_WAVE && !wave_search_fits(ctx))
     return fail(ctx, POMCP_E_UNSUPPORTED, "set_search_kernel: wave search scratch too large");
   if (kind == POMCP_SEARCH_WAVE && ctx->dp.tm)

@@ -191,7 +191,7 @@ struct Tree {
   // from the model stream first; the ego's next observation key
   __device__ void joint_step(uint32_t s0, uint32_t s1, int ego_a, int oth_a, uint32_t* n0,
                              uint32_t* n1, uint64_t* okey) {
-    const uint32_t j = Env::kStepDraws ? d_model(2) : 0u;
+    const uint32_t j = Env::kStepDraws ? d_model(Env::kStepRange) : 0u;
     double r;
     int done;
     Env::step(m, p.ego, s0, s1, (uint32_t)ego_a, (uint32_t)oth_a, j, n0, n1, &r, &done);
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void k_update(DevParams p) {
                 double r;
                 int done;
                 Env::step(sm, p.ego, hp.y, hp.z, (uint32_t)action, ao,
-                          Env::kStepDraws ? uniform_int(wm, 2u) : 0u, &n0, &n1, &r, &done);
+                          Env::kStepDraws ? uniform_int(wm, Env::kStepRange) : 0u, &n0, &n1, &r, &done);
                 const bool acc = valid && Env::obs_key(sm, p.ego, n0, n1) == obs;
                 const uint64_t am = __ballot(acc);
                 const int pa = __popcll(am & lt);
@@ -1970,7 +1970,7 @@ __global__ __launch_bounds__(256) void k_synthetic_step(DevParams p, uint64_t en
   Env::sample_initial(sm, [&](uint32_t n) { return env.model(n); }, &s0, &s1);
   const int a = p.in_actions[tree];
   const uint32_t ao = env.act(p.other, (uint32_t)p.A);
-  const uint32_t j = Env::kStepDraws ? env.model(2) : 0u;
+  const uint32_t j = Env::kStepDraws ? env.model(Env::kStepRange) : 0u;
   uint32_t n0, n1;
   double r;
   int done;

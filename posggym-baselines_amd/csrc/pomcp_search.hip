@@ -976,7 +976,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
           ret = 0.0;
           phase = TP_BACKUP;
         } else {
-          const uint32_t j = take_mod(2);
+          const uint32_t j = take_mod(Env::kStepRange);
           const uint32_t ao = take_oth(s0, s1);
           uint4 st[kMaxA];
 #pragma unroll
@@ -1139,7 +1139,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
           ae = tmt->ego_uniform ? uniform_int(aw, (uint32_t)A)
                                 : (uint32_t)tm_choice(tmt->ego_cum[epol], tmt->ego_tot[epol], A, aw);
         else ae = uniform_int(aw, (uint32_t)A);
-        const uint32_t j = take_mod(2);
+        const uint32_t j = take_mod(Env::kStepRange);
         const uint32_t ao = take_oth(s0, s1);                       // other_policy.py:151
         uint32_t n0, n1;
         double r;
@@ -1441,15 +1441,19 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
 PB_SEARCH_INST(EnvDriving, 5, kTPB, 0)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB, 0)
 PB_SEARCH_INST(EnvCoopReaching, 5, kTPB, 0)
+PB_SEARCH_INST(EnvPredatorPrey, 5, kTPB, 0)
 PB_SEARCH_INST(EnvDriving, 5, kTPBSmall, 0)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall, 0)
 PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall, 0)
+PB_SEARCH_INST(EnvPredatorPrey, 5, kTPBSmall, 0)
 PB_SEARCH_INST(EnvDriving, 5, kTPB, 1)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB, 1)
 PB_SEARCH_INST(EnvCoopReaching, 5, kTPB, 1)
+PB_SEARCH_INST(EnvPredatorPrey, 5, kTPB, 1)
 PB_SEARCH_INST(EnvDriving, 5, kTPBSmall, 1)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall, 1)
 PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall, 1)
+PB_SEARCH_INST(EnvPredatorPrey, 5, kTPBSmall, 1)
 #undef PB_SEARCH_INST
 
 #endif  // PB_SEARCH_TU
@@ -1464,9 +1468,11 @@ PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall, 1)
 PB_SEARCH_INST(EnvDriving, 5, kTPB)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPB)
 PB_SEARCH_INST(EnvCoopReaching, 5, kTPB)
+PB_SEARCH_INST(EnvPredatorPrey, 5, kTPB)
 PB_SEARCH_INST(EnvDriving, 5, kTPBSmall)
 PB_SEARCH_INST(EnvPursuitEvasion, 4, kTPBSmall)
 PB_SEARCH_INST(EnvCoopReaching, 5, kTPBSmall)
+PB_SEARCH_INST(EnvPredatorPrey, 5, kTPBSmall)
 #undef PB_SEARCH_INST
 #endif  // PB_SEARCH_DL
 
@@ -1490,8 +1496,11 @@ __attribute__((visibility("hidden"))) const void* PB_DL_CAT(pb_search_kernel_dl,
     k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, 0, PB_SEARCH_DL>},   \
    {k_search<EnvCoopReaching, POMCP_SEL_PUCB, 5, T, 0, PB_SEARCH_DL>,      \
     k_search<EnvCoopReaching, POMCP_SEL_UCB, 5, T, 0, PB_SEARCH_DL>,       \
-    k_search<EnvCoopReaching, POMCP_SEL_UNIFORM, 5, T, 0, PB_SEARCH_DL>}}
-  static const KFn table[2][3][3] = {PB_SEARCH_ROW(kTPB), PB_SEARCH_ROW(kTPBSmall)};
+    k_search<EnvCoopReaching, POMCP_SEL_UNIFORM, 5, T, 0, PB_SEARCH_DL>},     \
+   {k_search<EnvPredatorPrey, POMCP_SEL_PUCB, 5, T, 0, PB_SEARCH_DL>,      \
+    k_search<EnvPredatorPrey, POMCP_SEL_UCB, 5, T, 0, PB_SEARCH_DL>,       \
+    k_search<EnvPredatorPrey, POMCP_SEL_UNIFORM, 5, T, 0, PB_SEARCH_DL>}}
+  static const KFn table[2][4][3] = {PB_SEARCH_ROW(kTPB), PB_SEARCH_ROW(kTPBSmall)};
 #undef PB_SEARCH_ROW
   return reinterpret_cast<const void*>(table[small][e][sel]);
 }
@@ -1519,8 +1528,11 @@ __attribute__((visibility("hidden"))) const void* pb_search_kernel(int row, int 
     k_search<EnvPursuitEvasion, POMCP_SEL_UNIFORM, 4, T, TM>},                                    \
    {k_search<EnvCoopReaching, POMCP_SEL_PUCB, 5, T, TM>,                                          \
     k_search<EnvCoopReaching, POMCP_SEL_UCB, 5, T, TM>,                                           \
-    k_search<EnvCoopReaching, POMCP_SEL_UNIFORM, 5, T, TM>}}
-  static const KFn table[4][3][3] = {PB_SEARCH_ROW(kTPB, 0), PB_SEARCH_ROW(kTPBSmall, 0),
+    k_search<EnvCoopReaching, POMCP_SEL_UNIFORM, 5, T, TM>},                                      \
+   {k_search<EnvPredatorPrey, POMCP_SEL_PUCB, 5, T, TM>,                                          \
+    k_search<EnvPredatorPrey, POMCP_SEL_UCB, 5, T, TM>,                                           \
+    k_search<EnvPredatorPrey, POMCP_SEL_UNIFORM, 5, T, TM>}}
+  static const KFn table[4][4][3] = {PB_SEARCH_ROW(kTPB, 0), PB_SEARCH_ROW(kTPBSmall, 0),
                                      PB_SEARCH_ROW(kTPB, 1), PB_SEARCH_ROW(kTPBSmall, 1)};
 #undef PB_SEARCH_ROW
   return reinterpret_cast<const void*>(table[row][e][sel]);

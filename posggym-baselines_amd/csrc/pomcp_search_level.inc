@@ -6,7 +6,7 @@
 // Expects D (constexpr int) and dc (DepthC<D>) in scope.
       if (phase == TP_LEVEL) {
         const uint4* const ap = reinterpret_cast<const uint4*>(an + (int64_t)blk * blk_bytes);
-        const uint32_t j = take_mod(2);
+        const uint32_t j = take_mod(Env::kStepRange);
         const uint32_t ao = take_oth(s0, s1);
         PT_MARK(8);
         // the node line, prefetched by descend(): this arrival's N (its visits

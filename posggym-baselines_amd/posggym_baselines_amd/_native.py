@@ -35,6 +35,7 @@ SEARCH_AUTO, SEARCH_LANE, SEARCH_WAVE = 0, 1, 2   # pomcp_search_kernel
 ENV_DRIVING = 1
 ENV_PURSUIT_EVASION = 2
 ENV_COOPERATIVE_REACHING = 3   # created through pomcp_create_env with a PomcpCrGrid
+ENV_PREDATOR_PREY = 4          # created through pomcp_create_env with a PomcpPpGrid
 
 STATUS_NAMES = {
     POMCP_E_INVALID: "POMCP_E_INVALID",
@@ -91,6 +92,17 @@ class PomcpCrGrid(C.Structure):
         ("pad", C.c_int32),
         ("goal", (C.c_uint8 * 2) * 4),
         ("goal_value", C.c_double * 4),
+    ]
+
+
+class PomcpPpGrid(C.Structure):
+    _fields_ = [
+        ("size", C.c_int32),
+        ("num_prey", C.c_int32),
+        ("prey_strength", C.c_int32),
+        ("obs_dim", C.c_int32),
+        ("start", (C.c_uint8 * 2) * 8),
+        ("capture_reward", C.c_double),
     ]
 
 
@@ -399,6 +411,15 @@ SIGNATURES = [
     ("pomcp_cr_obs", C.c_int, [C.POINTER(PomcpCrGrid), _PU32, _PU64]),
     ("pomcp_cr_sample_agent_initial_state", C.c_int,
      [C.POINTER(PomcpCrGrid), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, _PU32, _PU32]),
+    ("pomcp_pp_sample_initial_state", C.c_int,
+     [C.POINTER(PomcpPpGrid), C.c_uint64, C.c_uint32, _PU32, _PU32]),
+    ("pomcp_pp_step", C.c_int, [C.POINTER(PomcpPpGrid), _PU32, _P32, C.c_uint64, C.c_uint32, _PU32,
+                                _PU32, _PD, _P32, _PU64]),
+    ("pomcp_debug_pp_step_draw", C.c_int, [C.POINTER(PomcpPpGrid), _PU32, _P32, C.c_uint32, _PU32,
+                                           _PD, _P32, _PU64, _P32, _P32]),
+    ("pomcp_pp_obs", C.c_int, [C.POINTER(PomcpPpGrid), _PU32, _PU64]),
+    ("pomcp_pp_sample_agent_initial_state", C.c_int,
+     [C.POINTER(PomcpPpGrid), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, _PU32, _PU32]),
     ("pomcp_host_cr_policy_actions", C.c_int,
      [C.POINTER(PomcpCrGrid), C.c_int64, _PU32, C.c_int32, _P32]),
     ("pomcp_philox_words", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,

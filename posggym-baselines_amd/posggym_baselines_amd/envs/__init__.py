@@ -1,5 +1,5 @@
 """Environment models the GPU engine implements (Driving-v1, PursuitEvasion-v1,
-CooperativeReaching-v0) and the recognition of a posggym-style ``env.model``."""
+CooperativeReaching-v0, PredatorPrey-v0) and the recognition of a posggym-style ``env.model``."""
 from posggym_baselines_amd.envs.driving import (  # noqa: F401
     GRIDS,
     DrivingModel,
@@ -7,6 +7,7 @@ from posggym_baselines_amd.envs.driving import (  # noqa: F401
     unpack_obs,
 )
 from posggym_baselines_amd.envs.cooperative_reaching import CooperativeReachingModel  # noqa: F401
+from posggym_baselines_amd.envs.predator_prey import PredatorPreyModel  # noqa: F401
 from posggym_baselines_amd.envs.pursuit_evasion import PursuitEvasionModel  # noqa: F401
 
 # posggym registrations the engine restates, with the env kwargs each accepts
@@ -22,6 +23,11 @@ _SUPPORTED = {
     "CooperativeReaching-v0": (CooperativeReachingModel, {"size": 5, "num_goals": 4,
                                                           "mode": "original",
                                                           "obs_distance": None}),
+    # (open grids "5x5" and "10x10", two predators, cooperative only: the model's
+    # constructor raises NotImplementedError for anything else)
+    "PredatorPrey-v0": (PredatorPreyModel, {"grid": "10x10", "num_predators": 2, "num_prey": 3,
+                                            "cooperative": True, "prey_strength": None,
+                                            "obs_dim": 2}),
 }
 # posggym env kwargs that do not change the generative model
 _IGNORED_KWARGS = {"render_mode", "max_episode_steps"}
@@ -58,7 +64,7 @@ def engine_model(model):
     if unknown:
         raise NotImplementedError(f"{env_id}: unsupported env kwargs {sorted(unknown)}")
     args = dict(defaults, **kwargs)
-    if "obs_dim" in args:
+    if "obs_dim" in args and env_id != "PredatorPrey-v0":    # (Driving-v1's triple; PredatorPrey's is an int)
         args["obs_dim"] = tuple(args["obs_dim"])
     if isinstance(args.get("grid"), str) and args["grid"] not in GRIDS and \
             env_id == "Driving-v1":

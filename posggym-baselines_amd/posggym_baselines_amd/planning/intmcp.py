@@ -47,7 +47,7 @@ import psutil
 from posggym_baselines_amd.envs import engine_model
 
 # environments the lane-per-tree POMCP engine runs and the I-NTMCP kernels do not
-_NO_INTMCP = ("CooperativeReaching-v0",)
+_NO_INTMCP = ("CooperativeReaching-v0", "PredatorPrey-v0")
 
 
 def _intmcp_model(model):
