@@ -690,11 +690,20 @@ int pomcp_host_belief_acc(const pomcp_belief_counts* counts, int32_t mixture_ind
  * POMCP_POLICY_CR_GOAL is the CooperativeReaching-v0 heuristic agent
  * (csrc/cooperative_reaching.h cr_goal_action; the registry ids
  * CooperativeReaching-v0/H{1..5}-v0): param0 is the rule 0..4 that picks its
- * target goal from its start cell, param1 must be 0.  (Kind 2 is unassigned.) */
+ * target goal from its start cell, param1 must be 0.
+ * POMCP_POLICY_PP_HEURISTIC is the PredatorPrey-v0 heuristic agent
+ * (csrc/predator_prey_policy.h; the registry ids PredatorPrey-v0/H{1,2,3}-v0):
+ * param0 is the rule 0..2 that picks its target (the nearest prey it sees; the
+ * other predator first; the prey the other predator is nearest to), param1 must
+ * be 0.  It is a STOCHASTIC reactive kind: the rule gives a distribution over up
+ * to four moves that depends on the state, and the word of the agent's stream,
+ * which the deterministic kinds take and ignore, picks from it as
+ * random.choices does from a fixed row.  (Kinds 2 and 4 are unassigned.) */
 enum {
   POMCP_POLICY_FIXED = 0,
   POMCP_POLICY_DRIVING_SHORTEST_PATH = 1,
-  POMCP_POLICY_CR_GOAL = 3
+  POMCP_POLICY_CR_GOAL = 3,
+  POMCP_POLICY_PP_HEURISTIC = 5
 };
 typedef struct pomcp_policy_kinds {
   int32_t kind[POMCP_MAX_TYPE_POLICIES];
@@ -755,6 +764,17 @@ int pomcp_host_driving_policy_actions(const pomcp_grid* grid, int64_t n, const u
  * rule never reads the other agent's word). */
 int pomcp_host_cr_policy_actions(const pomcp_cr_grid* grid, int64_t n, const uint32_t* own,
                                  int32_t rule, int32_t* out);
+/* The PredatorPrey-v0 heuristic agents on n states (w0[i], w1[i]) for predator
+ * `agent` under rule 0..2: out[i][0 .. 5) = the rule's action distribution, and
+ * out[i] = the action the word words[i] of the agent's stream draws from it
+ * (random.choices' bisection of the cumulative weights).  POMCP_E_INVALID: a
+ * null pointer, n < 0, a grid this build does not restate, agent not 0 / 1 or
+ * a bad rule. */
+int pomcp_host_pp_policy_pi(const pomcp_pp_grid* grid, int64_t n, const uint32_t* w0,
+                            const uint32_t* w1, int32_t agent, int32_t rule, double* out);
+int pomcp_host_pp_policy_actions(const pomcp_pp_grid* grid, int64_t n, const uint32_t* w0,
+                                 const uint32_t* w1, int32_t agent, int32_t rule,
+                                 const uint32_t* words, int32_t* out);
 /* pomcp_host_episode_step_pop with the population's kinds (NULL: exactly that
  * call). */
 int pomcp_host_episode_step_pop_kinds(int32_t env_id, const void* grid, int32_t ego,

@@ -17,6 +17,11 @@
 //   policy_action(m, agent, s0, s1, kind, p0, p1) a state-reactive policy's
 //                              action for `agent` (pomcp_policy_kinds;
 //                              PursuitEvasion has no reactive kinds)
+//   policy_draw(m, agent, s0, s1, kind, p0, p1, w) the same with the word w of
+//                              the agent's action stream, which a stochastic
+//                              kind (PredatorPrey's heuristics) draws with;
+//                              what the other agent's call sites call.  A
+//                              deterministic kind ignores w: policy_action
 //   kEgoKinds                  a reactive kind may be an EGO policy of the
 //                              type-based search (pomcp_set_type_ego_kinds)
 //   sample_initial(m, draw, &s0, &s1)             model.sample_initial_state
@@ -34,6 +39,7 @@
 #include "driving_policy.h"
 #include "driving_vec.h"
 #include "predator_prey.h"
+#include "predator_prey_policy.h"
 #include "pursuit_evasion.h"
 
 namespace pb {
@@ -68,6 +74,11 @@ struct EnvDriving {
                                                            uint32_t s1, int /*kind*/, int p0,
                                                            int p1) {
     return (uint32_t)drv_sp_action(m.g, agent == 0 ? s0 : s1, agent == 0 ? s1 : s0, p0, p1);
+  }
+  __device__ static __forceinline__ uint32_t policy_draw(const Model& m, int agent, uint32_t s0,
+                                                         uint32_t s1, int kind, int p0, int p1,
+                                                         uint32_t /*w*/) {
+    return policy_action(m, agent, s0, s1, kind, p0, p1);
   }
   template <class Draw>
   __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
@@ -127,6 +138,11 @@ struct EnvPursuitEvasion {
                                                            int, int, int) {
     return 0u;   // (no reactive kinds: pomcp_set_type_policy_kinds refuses them)
   }
+  __device__ static __forceinline__ uint32_t policy_draw(const Model& m, int agent, uint32_t s0,
+                                                         uint32_t s1, int kind, int p0, int p1,
+                                                         uint32_t /*w*/) {
+    return policy_action(m, agent, s0, s1, kind, p0, p1);
+  }
   template <class Draw>
   __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
     pe_sample_initial_state(m, draw, s0, s1);
@@ -167,6 +183,11 @@ struct EnvCoopReaching {
                                                            int /*p1*/) {
     return (uint32_t)cr_goal_action(m, agent == 0 ? s0 : s1, p0);
   }
+  __device__ static __forceinline__ uint32_t policy_draw(const Model& m, int agent, uint32_t s0,
+                                                         uint32_t s1, int kind, int p0, int p1,
+                                                         uint32_t /*w*/) {
+    return policy_action(m, agent, s0, s1, kind, p0, p1);
+  }
   template <class Draw>
   __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {
     cr_sample_initial_state(m, draw, s0, s1);
@@ -204,7 +225,13 @@ struct EnvPredatorPrey {
   }
   __device__ static __forceinline__ uint32_t policy_action(const Model&, int, uint32_t, uint32_t,
                                                            int, int, int) {
-    return 0u;   // (no reactive kinds: pomcp_set_type_policy_kinds refuses them)
+    return 0u;   // (no deterministic kinds, and no ego kinds: never reached)
+  }
+  // POMCP_POLICY_PP_HEURISTIC (the one kind: has_kind), rule p0, drawn with w
+  __device__ static __forceinline__ uint32_t policy_draw(const Model& m, int agent, uint32_t s0,
+                                                         uint32_t s1, int /*kind*/, int p0,
+                                                         int /*p1*/, uint32_t w) {
+    return (uint32_t)pp_heuristic_action(m, agent, s0, s1, p0, w);
   }
   template <class Draw>
   __device__ static void sample_initial(const Model& m, Draw draw, uint32_t* s0, uint32_t* s1) {

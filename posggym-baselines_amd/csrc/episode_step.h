@@ -21,8 +21,9 @@
 // agent's stream into an action as CPython's random.choices does
 // (PopulationAgents, planning/episodes.py).  A null population is the uniform
 // agent, draw for draw.  A member of a reactive kind (pomcp_policy_kinds)
-// acts on the true state before the joint action instead (E::policy_action);
+// acts on the true state before the joint action instead (E::policy_draw);
 // the word is still taken, so every counter advances as for a fixed member.
+// A deterministic kind ignores the word; PredatorPrey's heuristics draw with it.
 #ifndef PB_EPISODE_STEP_H_
 #define PB_EPISODE_STEP_H_
 #include <stdint.h>
@@ -32,6 +33,7 @@
 #include "driving_policy.h"
 #include "philox.h"
 #include "predator_prey.h"
+#include "predator_prey_policy.h"
 #include "pursuit_evasion.h"
 #include "../../include/pomcp.h"
 
@@ -70,6 +72,11 @@ struct EpDriving {
                                  int p0, int p1) {
     return drv_sp_action(m.g, agent == 0 ? s0 : s1, agent == 0 ? s1 : s0, p0, p1);
   }
+  // the same with the word of the agent's stream (a stochastic kind draws with it)
+  PB_HD static int policy_draw(const Model& m, int agent, uint32_t s0, uint32_t s1, int kind, int p0,
+                               int p1, uint32_t /*w*/) {
+    return policy_action(m, agent, s0, s1, kind, p0, p1);
+  }
 };
 
 struct EpPursuitEvasion {
@@ -94,6 +101,10 @@ struct EpPursuitEvasion {
   // (no reactive kinds: a population with one is refused before it gets here)
   PB_HD static bool has_kind(int /*kind*/) { return false; }
   PB_HD static int policy_action(const Model&, int, uint32_t, uint32_t, int, int, int) { return 0; }
+  PB_HD static int policy_draw(const Model& m, int agent, uint32_t s0, uint32_t s1, int kind, int p0,
+                               int p1, uint32_t /*w*/) {
+    return policy_action(m, agent, s0, s1, kind, p0, p1);
+  }
 };
 
 struct EpCoopReaching {
@@ -118,6 +129,10 @@ struct EpCoopReaching {
                                  int p0, int /*p1*/) {
     return cr_goal_action(m, agent == 0 ? s0 : s1, p0);
   }
+  PB_HD static int policy_draw(const Model& m, int agent, uint32_t s0, uint32_t s1, int kind, int p0,
+                               int p1, uint32_t /*w*/) {
+    return policy_action(m, agent, s0, s1, kind, p0, p1);
+  }
 };
 
 struct EpPredatorPrey {
@@ -140,16 +155,21 @@ struct EpPredatorPrey {
   PB_HD static uint64_t obs_key(const Model& m, int agent, uint32_t n0, uint32_t n1) {
     return pp_obs_key(m, agent, n0, n1);
   }
-  // (no reactive kinds: a population with one is refused before it gets here)
-  PB_HD static bool has_kind(int /*kind*/) { return false; }
-  PB_HD static int policy_action(const Model&, int, uint32_t, uint32_t, int, int, int) { return 0; }
+  // the heuristic agents H1 .. H3 (predator_prey_policy.h): a distribution that
+  // depends on the state, drawn with the word of the agent's stream
+  PB_HD static bool has_kind(int kind) { return kind == POMCP_POLICY_PP_HEURISTIC; }
+  PB_HD static int policy_draw(const Model& m, int agent, uint32_t s0, uint32_t s1, int /*kind*/,
+                               int p0, int /*p1*/, uint32_t w) {
+    return pp_heuristic_action(m, agent, s0, s1, p0, w);
+  }
 };
 
 // kind / parameters of one policy of a population or a mixture
 // (pomcp_policy_kinds), whichever environment has the kind: false for an
 // unknown kind or a parameter out of range.
 PB_HD bool policy_kind_ok(int kind, int p0, int p1) {
-  return drv_policy_kind_ok(kind, p0, p1) || cr_policy_kind_ok(kind, p0, p1);
+  return drv_policy_kind_ok(kind, p0, p1) || cr_policy_kind_ok(kind, p0, p1) ||
+         pp_policy_kind_ok(kind, p0, p1);
 }
 
 // A population's draw tables: random.choices' cumulative weights
@@ -161,7 +181,7 @@ struct EpPopTables {
   double tot[POMCP_MAX_TYPE_POLICIES];
   int32_t mix[POMCP_MAX_TYPE_POLICIES];
   // pomcp_policy_kinds: POMCP_POLICY_FIXED draws from cum / tot, a reactive
-  // kind acts by E::policy_action(kind, p0, p1)
+  // kind acts by E::policy_draw(kind, p0, p1, word)
   int32_t kind[POMCP_MAX_TYPE_POLICIES];
   int32_t p0[POMCP_MAX_TYPE_POLICIES], p1[POMCP_MAX_TYPE_POLICIES];
 };
@@ -320,7 +340,7 @@ PB_HD void episode_step(const typename E::Model& m, int ego, const pomcp_episode
   if (pop != nullptr) {
     const int k = policy_index >= 0 && policy_index < pop->n ? policy_index : 0;
     if (pop->kind[k] != POMCP_POLICY_FIXED)
-      a_oth = E::policy_action(m, other, s.v0, s.v1, pop->kind[k], pop->p0[k], pop->p1[k]);
+      a_oth = E::policy_draw(m, other, s.v0, s.v1, pop->kind[k], pop->p0[k], pop->p1[k], w_oth);
     else
       a_oth = ep_choice(pop->cum[k], pop->tot[k], (int)E::kA, w_oth);
   } else {

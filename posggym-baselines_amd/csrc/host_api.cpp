@@ -358,6 +358,31 @@ int pomcp_pp_obs(const pomcp_pp_grid* g, const uint32_t state[2], uint64_t obs_k
   return POMCP_OK;
 }
 
+// The heuristic agents' rule (predator_prey_policy.h), the code the kernels run.
+int pomcp_host_pp_policy_pi(const pomcp_pp_grid* g, int64_t n, const uint32_t* w0,
+                            const uint32_t* w1, int32_t agent, int32_t rule, double* out) {
+  if (!g || n < 0 || (n > 0 && (!w0 || !w1 || !out)) || (agent != 0 && agent != 1) ||
+      !pp_grid_ok(*g) || !pp_policy_kind_ok(POMCP_POLICY_PP_HEURISTIC, rule, 0))
+    return POMCP_E_INVALID;
+  PpModel m;
+  build_pp_model(*g, &m);
+  for (int64_t i = 0; i < n; ++i) pp_heuristic_pi(m, agent, w0[i], w1[i], rule, out + i * 5);
+  return POMCP_OK;
+}
+
+int pomcp_host_pp_policy_actions(const pomcp_pp_grid* g, int64_t n, const uint32_t* w0,
+                                 const uint32_t* w1, int32_t agent, int32_t rule,
+                                 const uint32_t* words, int32_t* out) {
+  if (!g || n < 0 || (n > 0 && (!w0 || !w1 || !words || !out)) || (agent != 0 && agent != 1) ||
+      !pp_grid_ok(*g) || !pp_policy_kind_ok(POMCP_POLICY_PP_HEURISTIC, rule, 0))
+    return POMCP_E_INVALID;
+  PpModel m;
+  build_pp_model(*g, &m);
+  for (int64_t i = 0; i < n; ++i)
+    out[i] = pp_heuristic_action(m, agent, w0[i], w1[i], rule, words[i]);
+  return POMCP_OK;
+}
+
 // ---------------------------------------------------------- host RNG streams
 
 int pomcp_philox_words(uint64_t seed, uint32_t tree, uint32_t stream, uint32_t first, int32_t n,

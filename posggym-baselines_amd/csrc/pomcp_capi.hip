@@ -857,7 +857,7 @@ int pomcp_set_type_policy_kinds(pomcp_ctx* ctx, const pomcp_policy_kinds* kinds)
   for (int j = 0; kinds && j < t.n_other; ++j) {
     if (!policy_kind_ok(kinds->kind[j], kinds->param0[j], kinds->param1[j]))
       return fail(ctx, POMCP_E_INVALID, "set_type_policy_kinds: kind 1 (caution 0..15, vmax 0..3), "
-                                        "kind 3 (rule 0..4, 0) or 0");
+                                        "kind 3 (rule 0..4, 0), kind 5 (rule 0..2, 0) or 0");
     if (kinds->kind[j] == POMCP_POLICY_FIXED) continue;
     bool has = false;
     with_episode_env(ctx, [&](auto e) { has = decltype(e)::has_kind(kinds->kind[j]); });

@@ -171,8 +171,9 @@ struct TmTables {
   int32_t meta_len[kTmMax];
   // pomcp_policy_kinds of the other-agent policies (pomcp_set_type_policy_kinds):
   // POMCP_POLICY_FIXED draws from oth_cum / oth_tot, a reactive kind acts by
-  // Env::policy_action(kind, p0, p1) on the running state; the word is taken
-  // either way
+  // Env::policy_draw(kind, p0, p1, word) on the running state; the word is taken
+  // either way (a deterministic kind ignores it, PredatorPrey's heuristics draw
+  // with it)
   int32_t oth_kind[kTmMax], oth_p0[kTmMax], oth_p1[kTmMax];
 };
 static_assert(kTmMax == kTmEgoMax, "tm_prior.h indexes TmTables::prior rows");

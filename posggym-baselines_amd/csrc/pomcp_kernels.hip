@@ -558,8 +558,8 @@ __global__ __launch_bounds__(256) void k_update(DevParams p) {
                 if (!p.tm || p.tmt->other_uniform)
                   ao = uniform_int(wa, (uint32_t)p.A);
                 else if (p.tmt->oth_kind[hp.w] != POMCP_POLICY_FIXED)
-                  ao = Env::policy_action(sm, p.other, hp.y, hp.z, p.tmt->oth_kind[hp.w],
-                                          p.tmt->oth_p0[hp.w], p.tmt->oth_p1[hp.w]);
+                  ao = Env::policy_draw(sm, p.other, hp.y, hp.z, p.tmt->oth_kind[hp.w],
+                                        p.tmt->oth_p0[hp.w], p.tmt->oth_p1[hp.w], wa);
                 else
                   ao = (uint32_t)tm_choice(p.tmt->oth_cum[hp.w], p.tmt->oth_tot[hp.w], p.A, wa);
                 uint32_t n0, n1;

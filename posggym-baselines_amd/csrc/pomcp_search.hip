@@ -386,8 +386,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(POMCP_WAVES
       if (tmt->other_uniform) return uniform_int(w, (uint32_t)A);
       // a state-reactive policy: by the running state (divergent per lane, no barrier)
       if (tmt->oth_kind[pid] != POMCP_POLICY_FIXED)
-        return Env::policy_action(sm, p.other, v0, v1, tmt->oth_kind[pid], tmt->oth_p0[pid],
-                                  tmt->oth_p1[pid]);
+        return Env::policy_draw(sm, p.other, v0, v1, tmt->oth_kind[pid], tmt->oth_p0[pid],
+                                tmt->oth_p1[pid], w);
       return (uint32_t)tm_choice(tmt->oth_cum[pid], tmt->oth_tot[pid], A, w);
     } else {
       return uniform_int(w, (uint32_t)A);

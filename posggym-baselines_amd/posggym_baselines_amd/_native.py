@@ -287,6 +287,7 @@ class PomcpEpisodePopState(C.Structure):
 
 POLICY_FIXED, POLICY_DRIVING_SHORTEST_PATH = 0, 1   # pomcp_policy_kinds.kind
 POLICY_CR_GOAL = 3                                  # (2 is unassigned)
+POLICY_PP_HEURISTIC = 5                             # (4 is unassigned)
 
 
 class PomcpPolicyKinds(C.Structure):
@@ -422,6 +423,10 @@ SIGNATURES = [
      [C.POINTER(PomcpPpGrid), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, _PU32, _PU32]),
     ("pomcp_host_cr_policy_actions", C.c_int,
      [C.POINTER(PomcpCrGrid), C.c_int64, _PU32, C.c_int32, _P32]),
+    ("pomcp_host_pp_policy_pi", C.c_int,
+     [C.POINTER(PomcpPpGrid), C.c_int64, _PU32, _PU32, C.c_int32, C.c_int32, _PD]),
+    ("pomcp_host_pp_policy_actions", C.c_int,
+     [C.POINTER(PomcpPpGrid), C.c_int64, _PU32, _PU32, C.c_int32, C.c_int32, _PU32, _P32]),
     ("pomcp_philox_words", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32,
                                      _PU32]),
     ("pomcp_host_log_table", C.c_int, [C.c_int64, C.c_int64, _PD]),

@@ -22,7 +22,7 @@ SEARCH_DL_SOURCE = os.path.join(CSRC, "pomcp_search_dl_tu.hip")
 SEARCH_DLS = (1, 2, 3)
 DEPS = SOURCES + [SEARCH_SOURCE, SEARCH_DL_SOURCE] + [os.path.join(CSRC, f) for f in
                   ("pomcp_kernels.hip", "pomcp_search.hip", "pomcp_search_level.inc", "pomcp_search_lds.hip", "pomcp_device.h", "tm_prior.h", "driving.h", "driving_policy.h",
-                   "driving_vec.h", "philox.h", "envs.h", "pursuit_evasion.h", "cooperative_reaching.h", "predator_prey.h", "host_exp.h", "host_exp_table.h", "host_api.cpp", "belief_stats.h", "belief_stats.hip", "episode_step.h", "pomcp_episode.hip", "episode_group.h", "pomcp_episode_group.hip", "episode_belief_acc.hip", "episode_queue.h", "pomcp_episode_queue.hip", "episode_group_queue.h", "pomcp_episode_group_queue.hip", "intmcp.hip", "intmcp_capi.hip", "intmcp_episode.h", "intmcp_episode.hip", "intmcp_episode_queue.hip", "host_ctx.h", "host_episodes.h")] + [
+                   "driving_vec.h", "philox.h", "envs.h", "pursuit_evasion.h", "cooperative_reaching.h", "predator_prey.h", "predator_prey_policy.h", "host_exp.h", "host_exp_table.h", "host_api.cpp", "belief_stats.h", "belief_stats.hip", "episode_step.h", "pomcp_episode.hip", "episode_group.h", "pomcp_episode_group.hip", "episode_belief_acc.hip", "episode_queue.h", "pomcp_episode_queue.hip", "episode_group_queue.h", "pomcp_episode_group_queue.hip", "intmcp.hip", "intmcp_capi.hip", "intmcp_episode.h", "intmcp_episode.hip", "intmcp_episode_queue.hip", "host_ctx.h", "host_episodes.h")] + [
     os.path.join(INCLUDE, "pomcp.h"), os.path.join(INCLUDE, "pomcp_debug.h"),
     os.path.join(INCLUDE, "intmcp.h")]
 

@@ -338,7 +338,7 @@ class PopulationAgents:
 
     def act(self, agent_id: str, state=None) -> int:
         import bisect
-        from posggym_baselines_amd.planning.policies import is_reactive
+        from posggym_baselines_amd.planning.policies import cumulative, is_reactive
         j = self._ctr[agent_id]
         self._ctr[agent_id] = j + 1
         pol = self.population[self.policy_index]
@@ -348,8 +348,13 @@ class PopulationAgents:
             if pol.agent_id != agent_id:
                 raise ValueError(f"{pol.policy_id} is agent {pol.agent_id!r}'s policy, not "
                                  f"{agent_id!r}'s")
-            return pol.action_from_state(state)
-        cum, total = self._tables[self.policy_index]
+            if not hasattr(pol, "pi_from_state"):
+                return pol.action_from_state(state)
+            # a stochastic reactive member (PreyHeuristicPolicy): the word draws
+            # from the distribution the rule gives in this state
+            cum, total = cumulative(pol.pi_from_state(state))
+        else:
+            cum, total = self._tables[self.policy_index]
         x = self._word(S_ENV_POLICY_BASE + int(agent_id), j) * 2.0 ** -32 * total
         return bisect.bisect_right(cum, x, 0, len(cum) - 1)
 

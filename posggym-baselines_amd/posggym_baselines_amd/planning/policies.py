@@ -17,7 +17,10 @@ CooperativeReaching-v0's goal heuristics H1 .. H5, which the episode kernels
 play as members of a test population (``other_agents=``) and the type-based
 search models as members of the other agent's mixture.  The goal heuristics
 can be the EGO's policies too -- a meta-policy's members, or a base planner's
-search policy (``ego_policy_kinds``).
+search policy (``ego_policy_kinds``).  ``PreyHeuristicPolicy``
+is PredatorPrey-v0's H1 .. H3: a STOCHASTIC reactive kind, whose distribution
+depends on the state and whose draw uses the word of the action stream
+(DESIGN.md §24).
 
 ``sample_action`` draws like ``random.choices(range(n), weights=probs)``
 (CPython's cumulative-weight bisection) on ``self.rng``; the engine makes the
@@ -418,10 +421,181 @@ class GoalHeuristicPolicy:
         pass
 
 
+# ----------------------------------------------------------------------------
+# The PredatorPrey-v0 heuristic agents (csrc/predator_prey_policy.h is the same
+# rule on the packed state words).
+
+# posggym.agents' ids of the reference's PredatorPrey population
+# (baseline_exps/env_data/PredatorPrey-v0/agents_P0.yaml) -> rule
+PREDATOR_PREY_POLICY_IDS = {
+    "PredatorPrey-v0/H1-v0": 0,    # the nearest prey, else the other predator, else explore
+    "PredatorPrey-v0/H2-v0": 1,    # close up on the other predator first, then hunt
+    "PredatorPrey-v0/H3-v0": 2,    # the prey the other predator is nearest to
+}
+_PP_DX = (0, 0, 0, -1, 1)          # DO_NOTHING, UP (y - 1), DOWN (y + 1), LEFT, RIGHT
+_PP_DY = (0, -1, 1, 0, 0)
+_PP_EMPTY, _PP_WALL, _PP_PREDATOR, _PP_PREY = 0, 1, 2, 3
+
+
+class PreyHeuristicPolicy:
+    """A PredatorPrey-v0 predator that heads for a target it sees and explores
+    at random when it sees none (the build's restatement of
+    ``PredatorPrey-v0/H{1,2,3}-v0``).  ``rule`` 0..2 is the only
+    thing the device sees of it (``kind_params``).  With ``seen`` = inside the
+    agent's observation window and distances Manhattan:
+
+        near    the seen prey nearest to the agent, ties by the window's
+                row-major order (smaller dy, then smaller dx)
+        rule 0  target = near, else the other predator if seen, else none
+        rule 1  target = the other predator if seen and further than 1, else near
+        rule 2  with a prey and the other predator seen: the seen prey nearest to
+                the other predator (ties: nearest to the agent, then window
+                order); else as rule 0
+
+    A move is free when its cell is on the grid and holds neither a prey nor
+    the other predator.  Without a target the agent is uniform over its free
+    moves; with one, over the free moves that bring it closer (at most two);
+    with none of either it does nothing.
+
+    This is a STOCHASTIC reactive policy: ``get_pi`` is a distribution that
+    depends on the state, and ``sample_action`` draws from it with
+    ``rng.choices`` -- the word of the agent's action stream that the
+    deterministic reactive policies take and ignore.  The policy is written the
+    posggym way: its state is the last observation (``{"obs"}``).  Everything
+    the rule reads lies inside the observation window, so ``pi_from_state``
+    gives the same distribution from the environment state alone, which is what
+    the kernels do."""
+
+    def __init__(self, model, agent_id: str, policy_id: str, rule: int, rng=None):
+        if getattr(model, "env_id", None) != "PredatorPrey-v0":
+            raise NotImplementedError(
+                f"prey heuristics are PredatorPrey-v0's, not "
+                f"{getattr(model, 'env_id', model)!r}'s")
+        if len(model.possible_agents) != 2:
+            raise NotImplementedError("prey heuristics act among two predators")
+        if isinstance(rule, bool) or int(rule) != rule or not 0 <= int(rule) <= 2:
+            raise ValueError(f"{policy_id}: rule must be 0..2, not {rule}")
+        self.model = model
+        self.agent_id = agent_id
+        self.policy_id = policy_id
+        self.rule = int(rule)
+        self.size = int(model.size)
+        self.obs_dim = int(model.obs_dim)
+        self.num_actions = model.action_spaces[agent_id].n
+        self.rng = rng if rng is not None else random.Random()
+
+    @classmethod
+    def from_id(cls, model, agent_id: str, policy_id: str, rng=None):
+        """The policy of one of ``PREDATOR_PREY_POLICY_IDS``."""
+        if policy_id not in PREDATOR_PREY_POLICY_IDS:
+            raise KeyError(f"{policy_id!r} is not one of {sorted(PREDATOR_PREY_POLICY_IDS)}")
+        return cls(model, agent_id, policy_id, PREDATOR_PREY_POLICY_IDS[policy_id], rng)
+
+    def kind_params(self):
+        """(``pomcp_policy_kinds`` kind, param0, param1)."""
+        from posggym_baselines_amd._native import POLICY_PP_HEURISTIC
+        return POLICY_PP_HEURISTIC, self.rule, 0
+
+    # -- the rule, on cells relative to the agent ----------------------------
+    def _decide(self, prey, mate, blocked):
+        """(what the agent heads for: "prey", "mate" or "explore", its candidate
+        moves).  ``prey``: the seen prey as (dx, dy); ``mate``: the other
+        predator as (dx, dy) or None when unseen; ``blocked(a)``: move ``a`` is
+        not free."""
+        man = lambda p, q=(0, 0): abs(p[0] - q[0]) + abs(p[1] - q[1])
+        window = lambda q: (man(q), q[1], q[0])
+        near = min(prey, key=window) if prey else None
+        first = near if near is not None else mate
+        if self.rule == 0:
+            target = first
+        elif self.rule == 1:
+            target = mate if mate is not None and man(mate) > 1 else near
+        elif prey and mate is not None:
+            target = min(prey, key=lambda q: (man(q, mate),) + window(q))
+        else:
+            target = first
+        cand = [a for a in (1, 2, 3, 4) if not blocked(a) and (
+            target is None or man((_PP_DX[a], _PP_DY[a]), target) < man(target))]
+        what = "explore" if target is None else ("mate" if target == mate else "prey")
+        return what, cand
+
+    def _pi(self, prey, mate, blocked):
+        cand = self._decide(prey, mate, blocked)[1] or [0]
+        return [1.0 / len(cand) if a in cand else 0.0 for a in range(self.num_actions)]
+
+    def _seen(self, obs):
+        if isinstance(obs, int) or hasattr(obs, "__index__"):
+            n = (2 * self.obs_dim + 1) ** 2
+            obs = tuple((int(obs) >> (2 * i)) & 3 for i in range(n))
+        d = self.obs_dim
+        rel = [(dx, dy) for dy in range(-d, d + 1) for dx in range(-d, d + 1) if (dx, dy) != (0, 0)]
+        cells = dict(zip(rel, obs))                  # (the last entry, the flag, has no cell)
+        prey = [c for c in rel if cells[c] == _PP_PREY]
+        mates = [c for c in rel if cells[c] == _PP_PREDATOR]
+        return (prey, mates[0] if mates else None,
+                lambda a: cells[(_PP_DX[a], _PP_DY[a])] != _PP_EMPTY)
+
+    def decision_from_obs(self, obs):
+        """``_decide`` on an observation (for the tests' and the goldens' branch
+        counts)."""
+        return self._decide(*self._seen(obs))
+
+    def pi_from_obs(self, obs):
+        """The distribution from an observation (the cell tuple, or its key)."""
+        return self._pi(*self._seen(obs))
+
+    def pi_from_state(self, state):
+        """The same distribution from the environment state: the two packed
+        words (the product model's states, csrc/predator_prey.h) or
+        ``(predator 0, predator 1, prey)`` with ``(x, y)`` entities and ``None``
+        for a caught prey."""
+        S, d, i = self.size, self.obs_dim, int(self.agent_id)
+        if isinstance(state[0], int) or hasattr(state[0], "__index__"):
+            w0, w1 = int(state[0]), int(state[1])
+            xy = lambda c: (c % S, c // S)
+            caught = (w0 >> 21) & 7
+            cells = ((w0 >> 7) & 127, (w0 >> 14) & 127, (w1 >> 7) & 127)
+            state = (xy(w0 & 127), xy(w1 & 127),
+                     tuple(None if (caught >> k) & 1 else xy(cells[k]) for k in range(3)))
+        (x, y), (ox, oy) = state[i], state[1 - i]
+        live = [(q[0] - x, q[1] - y) for q in state[2] if q is not None]
+        seen = lambda c: max(abs(c[0]), abs(c[1])) <= d
+        mate = (ox - x, oy - y)
+
+        def blocked(a):
+            c = (_PP_DX[a], _PP_DY[a])
+            return not (0 <= x + c[0] < S and 0 <= y + c[1] < S) or c in live or c == mate
+
+        return self._pi([q for q in live if seen(q)], mate if seen(mate) else None, blocked)
+
+    # -- the posggym.agents policy interface ---------------------------------
+    def get_initial_state(self):
+        return {"obs": None}
+
+    def get_next_state(self, action, obs, state):
+        return {"obs": obs}
+
+    def probs(self, state):
+        return self.pi_from_obs(state["obs"])
+
+    def get_pi(self, state) -> ActionDistribution:
+        return ActionDistribution({a: p for a, p in enumerate(self.probs(state))})
+
+    def sample_action(self, state) -> int:
+        return self.rng.choices(range(self.num_actions), weights=self.probs(state), k=1)[0]
+
+    def get_value(self, state) -> float:
+        raise NotImplementedError(f"{self.policy_id} has no value estimates")
+
+    def close(self):
+        pass
+
+
 def is_reactive(policy) -> bool:
     """Whether ``policy`` acts on the state (``ShortestPathPolicy``,
-    ``GoalHeuristicPolicy``) instead of drawing from a fixed distribution."""
-    return isinstance(policy, (ShortestPathPolicy, GoalHeuristicPolicy))
+    ``GoalHeuristicPolicy``, ``PreyHeuristicPolicy``) instead of drawing from a
+    fixed distribution."""
+    return isinstance(policy, (ShortestPathPolicy, GoalHeuristicPolicy, PreyHeuristicPolicy))
 
 
 def policy_kinds(model, policies):

@@ -2,6 +2,7 @@
 step of ``BatchedPOMCP.run_episodes``:
 
     python tools/predator_prey_timing.py [--trees 65536] [--sims 2048] [--out FILE]
+    python tools/predator_prey_timing.py --agents [--out FILE]
 
 Search: synthetic roots at the benchmark's configuration (bench.py: plain POMCP,
 ucb, depth limit 2, deferred cut-off records, no re-root arenas) on the
@@ -20,7 +21,13 @@ environments are timed at would need 50 MB of arena a tree.
 Episodes: ``--episode-trees`` x ``--episode-sims`` plain planners, one episode
 each against a uniform random other predator, ``until="all_done"``; the batch's
 wall time per batch step and the device time of its three kernels' groups
-(``pomcp_episodes_timing``)."""
+(``pomcp_episodes_timing``).
+
+``--agents`` times the heuristic agents H1 .. H3 instead:
+the type-based search (IPOMCP, pucb, a three-member mixture) on
+``--episode-trees`` x ``--episode-sims`` with three fixed members and with
+{H1, H2, H3}, and one ``run_episodes`` batch of plain planners against the
+population {H1, H2, H3}."""
 import argparse
 import json
 import math
@@ -74,16 +81,62 @@ def time_search(model, trees, sims, max_blocks):
     return rec
 
 
-def time_episodes(model, trees, sims, first_seed):
+def heuristics(model, other="1"):
+    from posggym_baselines_amd.planning.policies import (PREDATOR_PREY_POLICY_IDS,
+                                                         PreyHeuristicPolicy)
+    return [PreyHeuristicPolicy.from_id(model, other, pid) for pid in PREDATOR_PREY_POLICY_IDS]
+
+
+def time_type_search(model, trees, sims, reactive):
+    """One warmed-up type-based search from the initial belief of one
+    observation: a mixture of three fixed rows, or of H1 .. H3."""
+    import numpy as np
+    import torch
+    from posggym_baselines_amd.planning import (MCTSConfig, OtherAgentMixturePolicy,
+                                                RandomSearchPolicy)
+    from posggym_baselines_amd.planning.engine import PomcpEngine
+    from posggym_baselines_amd.planning.ipomcp import base_type_tables
+    from posggym_baselines_amd.planning.policies import FixedDistributionPolicy
+    cfg = MCTSConfig(seed=0, num_sims=sims, **dict(CFG, action_selection="pucb",
+                                                   state_belief_only=False))
+    rows = ([0.2] * 5, [0.1, 0.1, 0.1, 0.6, 0.1], [0.3, 0.1, 0.1, 0.4, 0.1])
+    members = heuristics(model) if reactive else [
+        FixedDistributionPolicy(model, "1", f"o{k}", r) for k, r in enumerate(rows)]
+    mix = OtherAgentMixturePolicy(model, "1", {p.policy_id: p for p in members})
+    tp = base_type_tables(model, "0", cfg, {"1": mix}, RandomSearchPolicy(model, "0"))
+    model.seed(1000)
+    key = model.obs_key(model.sample_initial_obs(model.sample_initial_state())["0"])
+    out = []
+    for _ in range(2):                               # the first engine is the warm-up
+        eng = PomcpEngine(model, "0", cfg, num_trees=trees, num_sims=sims, searches=1,
+                          type_policies=tp)
+        try:
+            eng.reset()
+            eng.update(np.full(trees, -1, dtype=np.int32), np.full(trees, key, dtype=np.uint64))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.search(sims)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            done = sum(s.num_sims for s in eng.root_stats())
+        finally:
+            eng.close()
+        out.append({"trees": trees, "sims": sims, "reactive": bool(reactive), "search_wall_ms": ms,
+                    "simulations_per_s": done / ms * 1e3})
+    return out[1]
+
+
+def time_episodes(model, trees, sims, first_seed, other_agents=None):
     from posggym_baselines_amd.planning import BatchedPOMCP, MCTSConfig
     cfg = MCTSConfig(seed=0, num_sims=sims, **CFG)
     steps = model.spec.max_episode_steps
     bp = BatchedPOMCP(model, "0", cfg, trees, sims, searches=steps, reroot=True)
     try:
-        bp.run_episodes(range(first_seed, first_seed + trees), until="all_done")   # warm-up batch
+        bp.run_episodes(range(first_seed, first_seed + trees), until="all_done",
+                        other_agents=other_agents)   # warm-up batch
         t0 = time.perf_counter()
         rows = bp.run_episodes(range(first_seed + trees, first_seed + 2 * trees),
-                               until="all_done")
+                               until="all_done", other_agents=other_agents)
         wall = time.perf_counter() - t0
         (upd, search, step), n = bp.engine.episodes_timing()
     finally:
@@ -102,12 +155,29 @@ def main():
                     help="simulations per root; the arena is sims + 64 blocks a tree (see above)")
     ap.add_argument("--episode-trees", type=int, default=4096)
     ap.add_argument("--episode-sims", type=int, default=256)
+    ap.add_argument("--agents", action="store_true",
+                    help="time the heuristic agents H1 .. H3 instead (see above)")
     ap.add_argument("--out", default="-")
     args = ap.parse_args()
     import torch
     from posggym_baselines_amd.envs import DrivingModel, PredatorPreyModel
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     rec = {"device": torch.cuda.get_device_name(0), "kwargs": REF_KWARGS, "search": {}}
+    if args.agents:
+        model = PredatorPreyModel(**REF_KWARGS)
+        for name, reactive in (("fixed_mixture", False), ("heuristic_mixture", True)):
+            rec["search"][name] = time_type_search(model, args.episode_trees, args.episode_sims,
+                                                   reactive)
+            print(name, json.dumps(rec["search"][name]), flush=True)
+        for name, pop in (("episodes_uniform", None), ("episodes_heuristics", heuristics(model))):
+            rec[name] = time_episodes(PredatorPreyModel(**REF_KWARGS), args.episode_trees,
+                                      args.episode_sims, 3000, pop)
+            print(name, json.dumps(rec[name]), flush=True)
+        if args.out != "-":
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec) + "\n")
+        return 0
     for name, model in (("PredatorPrey-v0", PredatorPreyModel(**REF_KWARGS)),
                         ("Driving-v1", DrivingModel())):
         rec["search"][name] = time_search(model, args.trees, args.sims, args.sims + 64)
